@@ -16,8 +16,15 @@ times, `host_to_host_checks_per_s`, never `value`).
 Under torchrun each rank drives its own GPU; `python bench.py --gpus N` in one process
 drives N GPUs through ketogpu_multi (one host thread per GPU for the resident runs).
 
-    python bench.py [--gpus N --steps K --warmup W] [--small] [--no-cpu-baseline]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--small]
+    python bench.py --full [--gpus N --steps K --warmup W] [--no-cpu-baseline] ...
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what `value` needs: it sets up (the graph's snapshot and the resolved
+requests come from a cache file when one process drives the job, see load_inputs), warms up,
+times the K pipelined steps, writes the last step's answers with --dump-outputs and prints
+the line.  --full adds every leg beside it (host to host, one wait per call, pageable, the
+kernels' own times and roofline, the CPU baselines, the oracle parity of the whole batch).
 
 Rank 0 prints ONE JSON line (see the contract in README/DESIGN.md).
 """
@@ -45,6 +52,17 @@ def parse():
     p.add_argument("--steps", type=int, default=50)  # ~4 ms of resident calls: the barrier inside the timed region stays small
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--small", action="store_true", help="1/100-size graph for quick runs (not the metric)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside `value`: host to host, one wait per call, pageable, per-kernel "
+                        "times and roofline, CPU baselines, oracle parity (minutes of CPU work); --mode partitioned "
+                        "always runs all of its legs, with or without it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step answered as DIR/allowed.npy "
+                        "(float32, one value per request of the batch: 1.0 allowed, 0.0 denied; under torchrun "
+                        "each rank writes its own range as allowed_rank<r>.npy)")
+    p.add_argument("--cache-dir", default=os.path.join(ROOT, ".bench_cache"),
+                   help="where a plain run keeps the snapshot and the resolved requests of its workload "
+                        "(empty: build them in every run)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU work of the baseline sample")
     p.add_argument("--r2-sample", type=int, default=0,
@@ -134,34 +152,113 @@ def host_cores():
     return (min(nproc, quota) if quota else nproc), nproc, quota
 
 
+def config2_sizes(small, n_gpus):
+    """-> (workload name, requests per GPU, synth.rbac sizes) of the replicated line"""
+    scale = 100 if small else 1
+    per_gpu = 1_000_000 // (10 if small else 1)
+    sizes = dict(users=10_000_000 // scale, groups=100_000 // scale, docs=2_000_000 // scale,
+                 tuples=50_000_000 // scale, checks=per_gpu * n_gpus)
+    return "config2_rbac" + ("_small" if small else ""), per_gpu, sizes
+
+
+def last_step_copy(steps, copies):
+    """which of a GPU's `copies` rotating HBM batches the last of `steps` pipelined steps ran
+    on (step k runs on copy k mod copies)"""
+    return (steps - 1) % copies
+
+
+def inputs_hash(sizes):
+    """hash of the workload's sizes and seeds and of every native source (keto_amd/csrc,
+    include/ketogpu.h): the generator, the snapshot builder and the snapshot file format all
+    live there"""
+    import hashlib
+    from keto_amd import synth
+    h = hashlib.sha256(json.dumps([sorted(sizes.items()), synth.SEED, synth.SEED + 1]).encode())
+    csrc = os.path.join(ROOT, "keto_amd", "csrc")
+    for f in sorted(os.listdir(csrc)) + [os.path.join("..", "..", "include", "ketogpu.h")]:
+        h.update(f.encode())
+        with open(os.path.join(csrc, f), "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()[:16]
+
+
+def load_inputs(sizes, workload, cache_dir, need_workload):
+    """The run's inputs: the workload (generator handle; None when only the cache was read),
+    its snapshot and the resolved requests of the global batch, identical from run to run
+    (fixed seeds).  Generating the 50M rows and building the snapshot (single-threaded) is
+    some 20 s of host work that `value` never times, so a run that needs nothing
+    else of the workload (`need_workload` False) reads the finished snapshot
+    (ketogpu_snapshot_save / _load: the same arrays the builder made) and the resolved ids
+    from `cache_dir`, and writes them there first when they are missing.  The file names
+    carry the workload's sizes and seeds and a hash of the native sources, so another
+    generator or builder never reads these files; files of the same workload at other
+    sources are removed."""
+    from keto_amd import synth
+    from keto_amd.snapshot import Snapshot
+    namespaces = [("groups", 1), ("docs", 2)]  # synth.Workload's for kind "rbac"
+    t = {"generate": 0.0, "snapshot": 0.0, "cache_load": None}
+    stem = ids = None
+    if cache_dir:
+        prefix = f"{workload}_c{sizes['checks']}_"
+        stem = os.path.join(cache_dir, prefix + inputs_hash(sizes))
+        ids = stem + ".ids.npz"
+    if cache_dir and not need_workload and os.path.exists(stem + ".snap") and os.path.exists(ids):
+        t0 = time.time()
+        snap = Snapshot.load(stem + ".snap", namespaces)
+        with np.load(ids) as z:
+            roots, targets = z["roots"], z["targets"]
+        t["cache_load"] = round(time.time() - t0, 2)
+        log(f"snapshot and requests read from {os.path.relpath(stem, ROOT)}.* in {t['cache_load']:.1f}s")
+        return None, snap, roots, targets, t
+    t0 = time.time()
+    # every rank builds the same graph and the same global batch (same seeds)
+    w = synth.rbac(**sizes, seed=synth.SEED, check_seed=synth.SEED + 1)
+    t["generate"] = time.time() - t0
+    log(f"generated {w.counts} in {t['generate']:.1f}s")
+    t0 = time.time()
+    snap = Snapshot.from_columns(w.namespaces, w.columns)
+    t["snapshot"] = time.time() - t0
+    log(f"snapshot built in {t['snapshot']:.1f}s")
+    roots, targets = w.resolve(snap)
+    if cache_dir and not need_workload:
+        from keto_amd._lib import KetoError
+        t0 = time.time()
+        try:
+            os.makedirs(cache_dir, exist_ok=True)
+            # finished files of the same workload at other sources (never another run's *.tmp)
+            for f in os.listdir(cache_dir):
+                if (f.startswith(prefix) and f.endswith((".snap", ".ids.npz"))
+                        and not f.startswith(os.path.basename(stem) + ".")):
+                    os.remove(os.path.join(cache_dir, f))
+            tmp = f"{stem}.{os.getpid()}.tmp"
+            snap.save(tmp)
+            os.replace(tmp, stem + ".snap")
+            with open(tmp, "wb") as fh:
+                np.savez(fh, roots=roots, targets=targets)
+            os.replace(tmp, ids)  # last: a reader wants both files
+            log(f"snapshot and requests written to {os.path.relpath(stem, ROOT)}.* in {time.time() - t0:.1f}s")
+        except (OSError, KetoError) as err:  # a read-only tree or a full disk: the run goes on without
+            log(f"cache files not written ({err}): the next run generates again")
+    return w, snap, roots, targets, t
+
+
 def main():
     a = parse()
     rank, world, local = dist_init(a.gpus)
     if a.mode == "partitioned":
         return main_partitioned(a, rank, world, local)
     from keto_amd import _lib as L
-    from keto_amd import check, synth
-    from keto_amd.snapshot import Snapshot
+    from keto_amd import check
 
     # one process per GPU under torchrun (world = N), or one process driving N GPUs
     # through the replicated multi-GPU engine (world = 1, --gpus N): either way the
     # global batch of N x 1M requests is split into contiguous word ranges, one per GPU
     procs_gpus = a.gpus if world == 1 else 1
     n_gpus = world * procs_gpus
-    scale = 100 if a.small else 1
-    per_gpu = 1_000_000 // (10 if a.small else 1)
-    sizes = dict(users=10_000_000 // scale, groups=100_000 // scale, docs=2_000_000 // scale,
-                 tuples=50_000_000 // scale, checks=per_gpu * n_gpus)
-    t0 = time.time()
-    # every rank builds the same graph and the same global batch (same seeds)
-    w = synth.rbac(**sizes, seed=synth.SEED, check_seed=synth.SEED + 1)
-    t_gen = time.time() - t0
-    log(f"generated {w.counts} in {t_gen:.1f}s")
-    t0 = time.time()
-    snap = Snapshot.from_columns(w.namespaces, w.columns)
-    t_snap = time.time() - t0
-    log(f"snapshot built in {t_snap:.1f}s")
-    roots_all, targets_all = w.resolve(snap)
+    workload, per_gpu, sizes = config2_sizes(a.small, n_gpus)
+    # (the cache files are read and written by a job of one process only)
+    w, snap, roots_all, targets_all, t_setup = load_inputs(sizes, workload, a.cache_dir if world == 1 else "",
+                                                           need_workload=a.full)
     b, e = check.MultiEngine.ranges(len(roots_all), world)[rank]
     roots, targets = roots_all[b:e], targets_all[b:e]
     n = len(roots)
@@ -183,6 +280,102 @@ def main():
     # candidate first stage and keep the fastest; done here so the timed steps never do it
     for _ in range(2):
         step()
+
+    # `value`: the same batch resident in HBM on every GPU of the job (uploaded before the
+    # timed region; results stay in HBM), K steps between barriers + device syncs, max over
+    # ranks.  One process driving several GPUs runs one host thread per GPU.
+    rng = check.MultiEngine.ranges(n, procs_gpus) if procs_gpus > 1 else [(0, n)]
+    engs = [eng.engine(i) for i in range(procs_gpus)] if procs_gpus > 1 else [eng0]
+    qs = [e_.upload(roots[b_:e_r], targets[b_:e_r]) for e_, (b_, e_r) in zip(engs, rng)]
+
+    # pipelined: the K steps enqueued without a host wait per call
+    # (ketogpu_queries_run_async: the engine proves no request can need the second stage),
+    # one wait per GPU at the end, barrier + device sync on both sides — batch k+1 enqueued
+    # while batch k runs, as a server pipelines its batches.  PIPE_COPIES HBM copies of the
+    # GPU's batch rotate (a server's consecutive batches have their own result words): calls
+    # rotate over the engine's two streams, so a call's dense pass overlaps the next call's
+    # first stage
+    copies = [[qq] + [e_.upload(roots[b_:e_r], targets[b_:e_r]) for _ in range(PIPE_COPIES - 1)]
+              for qq, e_, (b_, e_r) in zip(qs, engs, rng)]
+    # warm-up: every copy's first call (synchronized, clears), then W steps as the timed ones
+    for cs in copies:
+        for qq in cs:
+            qq.run()
+
+    def pipelined(cs, e_, steps):
+        nq = 0
+        for k in range(steps):
+            nq += cs[k % len(cs)].run(pipelined=True)
+        e_.wait()
+        return nq
+
+    def pipelined_all(steps):
+        queued = [0] * len(qs)
+        if len(qs) == 1:
+            queued[0] = pipelined(copies[0], engs[0], steps)
+        else:
+            import threading
+
+            def _p(i):
+                queued[i] = pipelined(copies[i], engs[i], steps)
+            ths = [threading.Thread(target=_p, args=(i,)) for i in range(len(qs))]
+            for th in ths:
+                th.start()
+            for th in ths:
+                th.join()
+        return queued
+    pipelined_all(a.warmup)
+    torch.cuda.synchronize()
+    barrier(world)
+    t0 = time.perf_counter()
+    queued = pipelined_all(a.steps)
+    torch.cuda.synchronize()
+    barrier(world)
+    dt_pipe = max_over_ranks(time.perf_counter() - t0, world)
+    pipe_value = len(roots_all) * a.steps / dt_pipe
+    log(f"{a.steps} pipelined HBM-resident steps in {dt_pipe:.4f}s ({sum(queued)} calls queued without a wait)")
+    if a.dump_outputs:
+        # the answers of the last timed step: step k ran on copy k mod PIPE_COPIES of each GPU
+        last = np.concatenate([cs[last_step_copy(a.steps, len(cs))].download() for cs in copies])
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        name = "allowed.npy" if world == 1 else f"allowed_rank{rank}.npy"
+        np.save(os.path.join(a.dump_outputs, name), last.astype(np.float32))
+        log(f"{len(last)} answers of the last timed step written to {os.path.join(a.dump_outputs, name)}")
+
+    line = {
+        "metric": METRIC, "value": round(pipe_value, 1), "unit": "checks/s", "n_gpus": n_gpus, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(dt_pipe / a.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u32 ids / u64 bitmasks (integer)",
+        "data": "synthetic: config #2 RBAC generator (keto_amd/csrc/synth.cpp), seed 0x4B45544F",
+        "config": {"workload": workload, **sizes,
+                   "checks_per_gpu": per_gpu,
+                   "mode": "replicated graph, query batch split into contiguous word ranges",
+                   "parallelism": (f"query-shard x{n_gpus}" + (" (one process, ketogpu_multi)" if procs_gpus > 1
+                                                             else " (one process per GPU)" if world > 1 else ""))},
+        "timing": ("value: requests resident in HBM, PCIe legs excluded: per step one batch call per GPU over "
+                   "its range, enqueued without a host wait per call (ketogpu_queries_run_async: validation at "
+                   f"upload, traversal, result bits left in HBM; {PIPE_COPIES} HBM copies of the batch rotate, "
+                   "calls rotate over the engine's two streams), one wait per GPU after the K steps, barrier + "
+                   "device sync "
+                   f"on both sides, max over ranks; {sum(queued)} of {a.steps * len(qs)} calls queued without a "
+                   "wait; W warm-up steps of the same kind before; snapshot build and upload excluded.  "
+                   "SURVEY 8(d)'s number is host_to_host_checks_per_s (--full)"),
+        "full": a.full,
+        "setup_s": {"generate": round(t_setup["generate"], 2), "snapshot": round(t_setup["snapshot"], 2),
+                    "cache_load": t_setup["cache_load"]},
+        "snapshot": {k: v for k, v in snap.stats().items() if k.startswith("num_")},
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        barrier(world)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: every leg beside `value`
+    # host to host: the batch in pinned host memory in, result words into pinned memory out
     for _ in range(a.warmup):
         step()
     barrier(world)
@@ -199,6 +392,12 @@ def main():
     allowed = check.unpack_bits(out.array.copy(), n)
     host_value = len(roots_all) * a.steps / dt
     median_call = float(np.median(calls))
+    # every copy's bits of the pipelined steps
+    for cs, (b_, e_r) in zip(copies, rng):
+        for qq in cs:
+            assert np.array_equal(qq.download(), allowed[b_:e_r])
+        for qq in cs[1:]:
+            qq.close()
 
     # the same batch from pageable numpy arrays (no pinned staging): reported, not `value`
     c0 = time.perf_counter()
@@ -206,10 +405,10 @@ def main():
     t_pageable = time.perf_counter() - c0
     assert np.array_equal(got_pageable, allowed)
 
-    # the timed step's own first-stage kernel (the host-batch instantiation reading its
+    # the host-to-host step's own first-stage kernel (the host-batch instantiation reading its
     # requests from pinned memory): the same steps again with a timing event between the
-    # call's kernels, hipEvents on the engine's stream (not `value`: the events cost idle
-    # GPU time between the launches)
+    # call's kernels, hipEvents on the engine's stream (the events cost idle GPU time between
+    # the launches)
     host_runs = []
     if procs_gpus == 1:
         eng0.set_events(True)
@@ -219,12 +418,7 @@ def main():
         eng0.set_events(False)
         assert np.array_equal(check.unpack_bits(out.array.copy(), n), allowed)
 
-    # `value`: the same batch resident in HBM on every GPU of the job (uploaded before the
-    # timed region; results stay in HBM), K steps between barriers + device syncs, max over
-    # ranks.  One process driving several GPUs runs one host thread per GPU.
-    rng = check.MultiEngine.ranges(n, procs_gpus) if procs_gpus > 1 else [(0, n)]
-    engs = [eng.engine(i) for i in range(procs_gpus)] if procs_gpus > 1 else [eng0]
-    qs = [e_.upload(roots[b_:e_r], targets[b_:e_r]) for e_, (b_, e_r) in zip(engs, rng)]
+    # the same K resident steps with one host wait per call (ketogpu_queries_run)
     for qq in qs:
         for _ in range(a.warmup + 1):
             qq.run()
@@ -251,52 +445,6 @@ def main():
     log(f"{a.steps} HBM-resident steps in {dt_res:.4f}s")
     for qq, (b_, e_r) in zip(qs, rng):
         assert np.array_equal(qq.download(), allowed[b_:e_r])
-
-    # pipelined: the same K steps enqueued without a host wait per call
-    # (ketogpu_queries_run_async: the engine proves no request can need the second stage),
-    # one wait per GPU at the end, barrier + device sync on both sides — batch k+1 enqueued
-    # while batch k runs, as a server pipelines its batches.  PIPE_COPIES HBM copies of the
-    # GPU's batch rotate (a server's consecutive batches have their own result words): calls
-    # rotate over the engine's two streams, so a call's dense pass overlaps the next call's
-    # first stage
-    copies = [[qq] + [e_.upload(roots[b_:e_r], targets[b_:e_r]) for _ in range(PIPE_COPIES - 1)]
-              for qq, e_, (b_, e_r) in zip(qs, engs, rng)]
-    for cs in copies:
-        for qq in cs[1:]:
-            qq.run()
-
-    def pipelined(cs, e_):
-        nq = 0
-        for k in range(a.steps):
-            nq += cs[k % len(cs)].run(pipelined=True)
-        e_.wait()
-        return nq
-    queued = [0] * len(qs)
-    torch.cuda.synchronize()
-    barrier(world)
-    t0 = time.perf_counter()
-    if len(qs) == 1:
-        queued[0] = pipelined(copies[0], engs[0])
-    else:
-        import threading
-
-        def _p(i):
-            queued[i] = pipelined(copies[i], engs[i])
-        ths = [threading.Thread(target=_p, args=(i,)) for i in range(len(qs))]
-        for th in ths:
-            th.start()
-        for th in ths:
-            th.join()
-    torch.cuda.synchronize()
-    barrier(world)
-    dt_pipe = max_over_ranks(time.perf_counter() - t0, world)
-    pipe_value = len(roots_all) * a.steps / dt_pipe
-    log(f"{a.steps} pipelined HBM-resident steps in {dt_pipe:.4f}s ({sum(queued)} calls queued without a wait)")
-    for cs, (b_, e_r) in zip(copies, rng):
-        for qq in cs:
-            assert np.array_equal(qq.download(), allowed[b_:e_r])
-        for qq in cs[1:]:
-            qq.close()
     b0, e0 = rng[0]
     q = qs[0]
     # the kernels' own times: the same runs again with a timing event between the call's
@@ -397,23 +545,8 @@ def main():
         parity = dict(parity or {}, constructed_positives=int(pos.sum()),
                       constructed_positives_denied=int((pos & ~allowed.astype(bool)).sum()))
         out_line = {
-            "metric": METRIC, "value": round(pipe_value, 1), "unit": "checks/s", "n_gpus": n_gpus, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(dt_pipe / a.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u32 ids / u64 bitmasks (integer)",
-            "data": "synthetic: config #2 RBAC generator (keto_amd/csrc/synth.cpp), seed 0x4B45544F",
-            "config": {"workload": "config2_rbac" + ("_small" if a.small else ""), **sizes,
-                       "checks_per_gpu": per_gpu,
-                       "mode": "replicated graph, query batch split into contiguous word ranges",
-                       "parallelism": (f"query-shard x{n_gpus}" + (" (one process, ketogpu_multi)" if procs_gpus > 1
-                                                                 else " (one process per GPU)" if world > 1 else ""))},
-            "timing": ("value: requests resident in HBM, PCIe legs excluded: per step one batch call per GPU over "
-                       "its range, enqueued without a host wait per call (ketogpu_queries_run_async: validation at "
-                       f"upload, traversal, result bits left in HBM; {PIPE_COPIES} HBM copies of the batch rotate, "
-                       "calls rotate over the engine's two streams), one wait per GPU after the K steps, barrier + "
-                       "device sync "
-                       f"on both sides, max over ranks; {sum(queued)} of {a.steps * len(qs)} calls queued without a "
-                       "wait; every copy's bits checked after; snapshot build and upload excluded.  SURVEY 8(d)'s "
-                       "number is host_to_host_checks_per_s"),
+            **line,
+            "timing": line["timing"] + "; every copy's bits checked against the host-to-host answers after",
             "resident_call_checks_per_s": round(value, 1),
             "resident_call_ms_per_step": round(dt_res / a.steps * 1e3, 4),
             "resident_call_timing": ("the same K steps with one host wait per call (ketogpu_queries_run: round 5's "
@@ -448,8 +581,6 @@ def main():
                              if plan == "label" else None),
             "edges_per_check": round((st["interior_edges"] + st["rev_edges"]) / max(e0 - b0, 1), 2),
             "allowed_fraction": round(float(allowed.mean()), 4),
-            "setup_s": {"generate": round(t_gen, 2), "snapshot": round(t_snap, 2)},
-            "snapshot": {k: v for k, v in snap.stats().items() if k.startswith("num_")},
         }
         print(json.dumps(out_line), flush=True)
     barrier(world)
@@ -543,7 +674,7 @@ def main_partitioned(a, rank, world, local):
     barrier(world)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        got = step()
     barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world)
     if tier:
@@ -562,7 +693,6 @@ def main_partitioned(a, rank, world, local):
         fam = None
         t_timed = None
     else:
-        got = step()
         # measurement pass: the same step with every kernel launch bracketed by hipEvents
         before = eng.local.stats()["kernels"]
         eng.local.set_timing(True)
@@ -573,6 +703,10 @@ def main_partitioned(a, rank, world, local):
         after = eng.local.stats()
         fam = {k: {kk: after["kernels"][k][kk] - before[k][kk] for kk in ("bytes", "ms", "launches")}
                for k in after["kernels"]}
+    if a.dump_outputs:  # the answers of the last timed step (tier: this rank's own requests)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        name = "allowed.npy" if world == 1 else f"allowed_rank{rank}.npy"
+        np.save(os.path.join(a.dump_outputs, name), np.asarray(got).astype(np.float32))
     rss = [max_rss_gb()]
     if world > 1:
         import torch.distributed as dist

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <random>
 #include <string>
+#include <thread>
 #include <vector>
 
 namespace {
@@ -63,10 +64,13 @@ struct Col {
         data.insert(data.end(), p, p + n);
         off.push_back(data.size());
     }
-    void put_num(char prefix, uint64_t v) {
+    void put_num(char prefix, uint64_t v) {  // prefix + decimal digits (as "%c%llu")
         char b[24];
-        int n = snprintf(b, sizeof b, "%c%llu", prefix, (unsigned long long)v);
-        put(b, (size_t)n);
+        char *e = b + sizeof b, *p = e;
+        do *--p = (char)('0' + v % 10);
+        while (v /= 10);
+        *--p = prefix;
+        put(p, (size_t)(e - p));
     }
     void empty() { off.push_back(data.size()); }
 };
@@ -85,6 +89,68 @@ struct ks_rbac {
     Col rq_ns, rq_obj, rq_rel, rq_sid;
     uint64_t n_parent = 0, n_member = 0, n_grant = 0;
 };
+
+namespace {
+
+// The rows that `fn(part, item)` emits for every item, in the order of `items`, appended to
+// w's rows: the items are cut into contiguous ranges of about equal row counts
+// (`weight(item)`), each range is emitted by a thread into a part of its own, and the parts
+// are copied behind w's rows in range order — the same rows as the serial loop makes.
+template <class W, class F>
+void emit_parallel(ks_rbac *w, const std::vector<uint32_t> &items, W weight, F fn) {
+    const unsigned T = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    uint64_t total = 0;
+    for (uint32_t it : items) total += weight(it);
+    std::vector<size_t> cut{0};
+    uint64_t acc = 0;
+    for (size_t i = 0; i < items.size() && cut.size() < T; i++) {
+        acc += weight(items[i]);
+        if (acc >= total / T * cut.size()) cut.push_back(i + 1);
+    }
+    while (cut.size() <= T) cut.push_back(items.size());
+    cut[T] = items.size();
+    std::vector<ks_rbac> part(T);
+    auto on_threads = [&](auto body) {
+        std::vector<std::thread> th;
+        for (unsigned t = 1; t < T; t++) th.emplace_back(body, t);
+        body(0u);
+        for (auto &x : th) x.join();
+    };
+    on_threads([&](unsigned t) {
+        for (size_t i = cut[t]; i < cut[t + 1]; i++) fn(part[t], items[i]);
+    });
+    Col ks_rbac::*const cols[5] = {&ks_rbac::obj, &ks_rbac::rel, &ks_rbac::sid, &ks_rbac::ss_obj, &ks_rbac::ss_rel};
+    std::vector<uint64_t> row0(T + 1, w->ns.size());
+    std::vector<uint64_t> byte0[5];
+    for (unsigned t = 0; t < T; t++) row0[t + 1] = row0[t] + part[t].ns.size();
+    for (int c = 0; c < 5; c++) {
+        byte0[c].assign(T + 1, (w->*cols[c]).data.size());
+        for (unsigned t = 0; t < T; t++) byte0[c][t + 1] = byte0[c][t] + (part[t].*cols[c]).data.size();
+        (w->*cols[c]).data.resize(byte0[c][T]);
+        (w->*cols[c]).off.resize(row0[T] + 1);
+    }
+    w->ns.resize(row0[T]);
+    w->kind.resize(row0[T]);
+    w->ss_ns.resize(row0[T]);
+    on_threads([&](unsigned t) {
+        ks_rbac &p = part[t];
+        const uint64_t n = p.ns.size();
+        if (n) {
+            memcpy(w->ns.data() + row0[t], p.ns.data(), n * sizeof(int32_t));
+            memcpy(w->kind.data() + row0[t], p.kind.data(), n);
+            memcpy(w->ss_ns.data() + row0[t], p.ss_ns.data(), n * sizeof(int32_t));
+        }
+        for (int c = 0; c < 5; c++) {
+            const Col &s = p.*cols[c];
+            Col &d = w->*cols[c];
+            if (!s.data.empty()) memcpy(d.data.data() + byte0[c][t], s.data.data(), s.data.size());
+            for (uint64_t i = 0; i < n; i++) d.off[row0[t] + 1 + i] = byte0[c][t] + s.off[i + 1];
+        }
+        p = ks_rbac();
+    });
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -200,45 +266,50 @@ ks_rbac *ks_rbac_generate(const ks_rbac_params *p) {
     w->ns.reserve(total);
     w->kind.reserve(total);
     w->ss_ns.reserve(total);
-    auto row_set = [&](int32_t ns, char op, uint64_t o, const char *rel, char sp, uint64_t so, int32_t sns,
-                       const char *srel) {
-        w->ns.push_back(ns);
-        w->kind.push_back(1);
-        w->ss_ns.push_back(sns);
-        w->obj.put_num(op, o);
-        w->rel.put(rel, strlen(rel));
-        w->sid.empty();
-        w->ss_obj.put_num(sp, so);
-        w->ss_rel.put(srel, strlen(srel));
+    auto row_set = [](ks_rbac &t, int32_t ns, char op, uint64_t o, const char *rel, char sp, uint64_t so, int32_t sns,
+                      const char *srel) {
+        t.ns.push_back(ns);
+        t.kind.push_back(1);
+        t.ss_ns.push_back(sns);
+        t.obj.put_num(op, o);
+        t.rel.put(rel, strlen(rel));
+        t.sid.empty();
+        t.ss_obj.put_num(sp, so);
+        t.ss_rel.put(srel, strlen(srel));
     };
-    auto row_id = [&](int32_t ns, char op, uint64_t o, const char *rel, uint64_t u) {
-        w->ns.push_back(ns);
-        w->kind.push_back(0);
-        w->ss_ns.push_back(0);
-        w->obj.put_num(op, o);
-        w->rel.put(rel, strlen(rel));
-        w->sid.put_num('u', u);
-        w->ss_obj.empty();
-        w->ss_rel.empty();
+    auto row_id = [](ks_rbac &t, int32_t ns, char op, uint64_t o, const char *rel, uint64_t u) {
+        t.ns.push_back(ns);
+        t.kind.push_back(0);
+        t.ss_ns.push_back(0);
+        t.obj.put_num(op, o);
+        t.rel.put(rel, strlen(rel));
+        t.sid.put_num('u', u);
+        t.ss_obj.empty();
+        t.ss_rel.empty();
     };
+    // (the rows of one group or doc depend on nothing else: emitted on several threads)
     // namespace 1: groups (ordered by object string)
-    for (uint32_t g : lex_order(G)) {
-        auto &ch = children[g];
-        std::sort(ch.begin(), ch.end(), by_g);
-        for (uint32_t c : ch) row_set(1, 'g', g, "member", 'g', c, 1, "member");
-        auto &m = members[g];
-        std::sort(m.begin(), m.end(), by_u);
-        for (uint32_t u : m) row_id(1, 'g', g, "member", u);
-    }
+    emit_parallel(
+        w, lex_order(G), [&](uint32_t g) { return children[g].size() + members[g].size(); },
+        [&](ks_rbac &t, uint32_t g) {
+            auto &ch = children[g];
+            std::sort(ch.begin(), ch.end(), by_g);
+            for (uint32_t c : ch) row_set(t, 1, 'g', g, "member", 'g', c, 1, "member");
+            auto &m = members[g];
+            std::sort(m.begin(), m.end(), by_u);
+            for (uint32_t u : m) row_id(t, 1, 'g', g, "member", u);
+        });
     // namespace 2: docs
-    for (uint32_t d : lex_order(D)) {
-        auto &dg = doc_groups[d];
-        std::sort(dg.begin(), dg.end(), by_g);
-        for (uint32_t g : dg) row_set(2, 'd', d, "viewer", 'g', g, 1, "member");
-        auto &du = doc_users[d];
-        std::sort(du.begin(), du.end(), by_u);
-        for (uint32_t u : du) row_id(2, 'd', d, "viewer", u);
-    }
+    emit_parallel(
+        w, lex_order(D), [&](uint32_t d) { return doc_groups[d].size() + doc_users[d].size(); },
+        [&](ks_rbac &t, uint32_t d) {
+            auto &dg = doc_groups[d];
+            std::sort(dg.begin(), dg.end(), by_g);
+            for (uint32_t g : dg) row_set(t, 2, 'd', d, "viewer", 'g', g, 1, "member");
+            auto &du = doc_users[d];
+            std::sort(du.begin(), du.end(), by_u);
+            for (uint32_t u : du) row_id(t, 2, 'd', d, "viewer", u);
+        });
     // ---- checks
     if (p->check_seed) rng = Rng(p->check_seed);
     const uint64_t C = p->checks;

@@ -7,6 +7,7 @@ for v in "direct" "dma KETOGPU_PIPE_DMA=1" "dma128k KETOGPU_PIPE_DMA=1 KETOGPU_P
   name=${v%% *}; envs=${v#* }; [ "$name" = "$v" ] && envs=""
   env KETOGPU_UNITS=label $envs timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv \
     -d gpurun_out/tr_$name -o run -- python3 bench.py --no-cpu-baseline --parity sample --steps 5 --warmup 2 \
+    --full \
     > gpurun_out/tr_$name.log 2>&1 || { echo "$name failed"; tail -5 gpurun_out/tr_$name.log; exit 1; }
   python3 tools/timeline.py gpurun_out/tr_$name --calls 2 > gpurun_out/tl_$name.txt 2>&1 || true
 done
