@@ -103,10 +103,11 @@ def test_random_tables_match_oracle(seed, page_size, poison, collide, empty_ns, 
 
 @pytest.mark.parametrize("heads,permille", [("0,0", 0), ("8,8", 0), ("16,8", 0), ("32,32", 0), ("8,16", 250)])
 def test_label_heads_match_oracle(heads, permille, monkeypatch):
-    """plan label over lists of up to hundreds of entries (the family graph's wide closures):
-    every head size pair (8-word heads: most lists in the overflow region), with a share of
-    the S heads marked unlabelled (the second stage), on device, HBM-resident and pinned
-    host batches"""
+    """plan label over the family graph, whose lists fit a 32-word head (seed 92: at most 30
+    S and 25 P entries; at 32,32 four requests reach the dense pass, all denied): every head
+    size pair (8-word heads: most lists in the overflow region), with a share of the S heads
+    marked unlabelled (the second stage), on device, HBM-resident and pinned host batches.
+    Lists past the heads, the dense pass's stage and its prefetch: tests/test_label_lists.py"""
     monkeypatch.setenv("KETOGPU_UNITS", "label")
     monkeypatch.setenv("KETOGPU_LABEL_HEADS", heads)
     monkeypatch.setenv("KETOGPU_LABEL_REST_PERMILLE", str(permille))
