@@ -2613,32 +2613,33 @@ __device__ __forceinline__ bool label_find_e(const uint32_t *L, uint32_t x) {
 // x among the first E ascending entries at L (LDS, 16-byte aligned) in two dependent LDS
 // rounds: the last entries of the 8-entry blocks (independent reads) give x's block, whose 8
 // entries are then read at once (two 16-byte reads) — against the binary search's chain of
-// log2(E) dependent reads.  Words at positions >= E are never compared (the image row's
-// words past the head are not written).  lower: the entries below x instead
-template <int E, bool LOWER>
-__device__ __forceinline__ uint32_t label_block8(const uint32_t *L, uint32_t x) {
+// log2(E) dependent reads.  E = head - 4, so only the last block is short (4 entries): its
+// second half (the image row's words past the head, never written) is left out by one test
+// of the block.  Some word equals x <=> the smallest (word ^ x) is 0: one compare per half
+// (eight equalities OR-ed compile to a 16-bit mask built with v_cndmask and shifts: 10 more
+// VALU instructions per lookup)
+template <int E>
+__device__ __forceinline__ bool label_block8(const uint32_t *L, uint32_t x) {
+    static_assert(E % 8 == 4, "a head's inline entries");
     constexpr int NB = (E + 7) / 8;
     uint32_t blk = 0;
 #pragma unroll
     for (int b = 0; b + 1 < NB; b++) blk += L[8 * b + 7] < x;
-    const uint4 u = *reinterpret_cast<const uint4 *>(L + 8 * blk), v = *reinterpret_cast<const uint4 *>(L + 8 * blk + 4);
-    const uint32_t w[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-    uint32_t r = LOWER ? 8 * blk : 0u;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const bool in = 8 * blk + i < (uint32_t)E;
-        if (LOWER)
-            r += in && w[i] < x;
-        else
-            r |= in && w[i] == x;
+    const uint4 u = *reinterpret_cast<const uint4 *>(L + 8 * blk);
+    const bool lo = min(min(u.x ^ x, u.y ^ x), min(u.z ^ x, u.w ^ x)) == 0;
+    if constexpr (NB == 1) {
+        return lo;
+    } else {
+        const uint4 v = *reinterpret_cast<const uint4 *>(L + 8 * blk + 4);
+        const bool hi = min(min(v.x ^ x, v.y ^ x), min(v.z ^ x, v.w ^ x)) == 0;
+        return lo | (hi & (blk != (uint32_t)(NB - 1)));
     }
-    return r;
 }
 
 // x in the head image `row` (LDS) among its first E entries (H: the head's words)
-template <int E, int H, bool LOWER>
-__device__ __forceinline__ uint32_t label_lookup(const uint32_t *row, uint32_t x) {
-    return label_block8<E, LOWER>(row + kHeadFixed, x);
+template <int E, int H>
+__device__ __forceinline__ bool label_lookup(const uint32_t *row, uint32_t x) {
+    return label_block8<E>(row + kHeadFixed, x);
 }
 
 // KETO_LABEL_MEET: how the shorter inline landmark list meets the other head.  0 (default):
@@ -2699,25 +2700,48 @@ __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelG
     }
     wave_sync();  // (the images: this wave's own rows)
     bool hit = labelled && (smask & pmask) != 0;
-    // S's inline landmarks: its inline entries below Ni (the raw entries follow them)
-    const uint32_t es = !labelled ? 0u : KETO_LABEL_MEET == 2 ? label_lower_e<CS>(Se, L.ni) : label_lookup<CS, HS, true>(Sl, L.ni);
+    // this lane's words of the S head that are entries (the header is words 0-3 of the head:
+    // the first lane's, or with 2 words per lane the first two lanes')
+    const bool s_body = sub * SW >= kHeadFixed;
+    // S's inline landmarks: its inline entries below Ni (the raw entries follow them), counted
+    // in the registers (pads are 0xFFFFFFFF) and summed over the request's four lanes by DPP
+    uint32_t es = 0;
+#pragma unroll
+    for (int k = 0; k < SW; k++) es += (k >= (int)kHeadFixed || s_body) && sw[k] < L.ni;
+    es += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)es, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
+    es += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)es, 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
+    if (!labelled) es = 0;
     const uint32_t ep = min(np, CP);
+    // the one-edge test: a non-interior root among S's inline raw entries, each lane against
+    // its own words (a landmark is below Ni and a pad no node id: neither equals such a root)
+    {
+        bool head = false, body = false;
+#pragma unroll
+        for (int k = 0; k < SW; k++) (k < (int)kHeadFixed ? head : body) |= sw[k] == r;
+        hit |= labelled && r >= L.ni && (body | (head & s_body));
+    }
     // 1. the inline landmark prefixes: the shorter walked, round-robin over the request's
-    //    four lanes, each entry searched in the other; the one-edge test (a non-interior root
-    //    among S's inline raw entries) on the fourth lane
+    //    four lanes, each entry searched in the other
     if (labelled && !hit) {
         if (KETO_LABEL_MEET == 2) {
             if (es <= ep)
                 for (uint32_t k = sub; k < es && !hit; k += 4) hit = label_find_e<CP>(Pe, Se[k]);
             else
                 for (uint32_t k = sub; k < ep && !hit; k += 4) hit = label_find_e<CS>(Se, Pe[k]);
-            if (sub == 3 && !hit && r >= L.ni) hit = label_find_e<CS>(Se, r);
         } else {
-            if (es <= ep)
-                for (uint32_t k = sub; k < es && !hit; k += 4) hit = label_lookup<CP, HP, false>(Pl, Se[k]);
-            else
-                for (uint32_t k = sub; k < ep && !hit; k += 4) hit = label_lookup<CS, HS, false>(Sl, Pe[k]);
-            if (sub == 3 && !hit && r >= L.ni) hit = label_lookup<CS, HS, false>(Sl, r);
+            if constexpr (HS == HP) {
+                // equal heads: one loop, the walked list, its bound and the searched row per lane
+                // (a unit with requests of both kinds runs max, not max + max, rounds)
+                const bool ws = es <= ep;
+                const uint32_t *W = ws ? Se : Pe, *O = ws ? Pl : Sl;
+                const uint32_t e = ws ? es : ep;
+                for (uint32_t k = sub; k < e && !hit; k += 4) hit = label_lookup<CP, HP>(O, W[k]);
+            } else {  // (the lists' block counts differ: a loop each)
+                if (es <= ep)
+                    for (uint32_t k = sub; k < es && !hit; k += 4) hit = label_lookup<CP, HP>(Pl, Se[k]);
+                else
+                    for (uint32_t k = sub; k < ep && !hit; k += 4) hit = label_lookup<CS, HS>(Sl, Pe[k]);
+            }
         }
     }
     // 2. a request neither hit nor settled by its heads (labels.hpp): listed for
@@ -2748,8 +2772,11 @@ __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelG
     }
     const uint64_t bits = __ballot(hit);
     // statistics: 2 rows (heads) and the entries read (both lists and the masks) per request
-    const uint32_t rows = wave_sum_all(labelled && sub == 0 ? 2u : 0u);
-    const uint32_t ent = wave_sum_all(labelled && sub == 0 ? ns + np + kHeadFixed : 0u);
+    uint32_t rows = 0, ent = 0;
+    if (stats) {  // (wave-uniform; lean calls: none, so no reduction either)
+        rows = wave_sum_all(labelled && sub == 0 ? 2u : 0u);
+        ent = wave_sum_all(labelled && sub == 0 ? ns + np + kHeadFixed : 0u);
+    }
     // bit j of the unit's result = any of the request's four lanes (scalar bit compression)
     uint64_t x = bits | bits >> 1;
     x = (x | x >> 2) & 0x1111111111111111ull;
