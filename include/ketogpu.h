@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-#define KETOGPU_ABI_VERSION 9 /* 9: plan label in the two-tier mode (tier stats label_*);
+#define KETOGPU_ABI_VERSION 9 /* (packed24 request batches, ketogpu_*packed24* and
+                                    ketogpu_engine_last_request_path, are additions within
+                                    9: no existing entry point or struct layout changed)
+                                 9: plan label in the two-tier mode (tier stats label_*);
                                  8: 2-hop reachability labels (plan label), run stats
                                     label_* / rest_*;
                                  7: two-tier partitioned mode (ketogpu_core_*, ketogpu_tier_*);
@@ -354,6 +357,35 @@ int ketogpu_check(ketogpu_engine *e, const ketogpu_check_request *reqs, size_t n
 int ketogpu_check_ids(ketogpu_engine *e, const uint32_t *roots, const uint32_t *targets, size_t n,
                       uint64_t *allowed_bits, uint64_t *flagged_bits);
 
+/* Packed 24-bit request batches ("packed24"): 6 bytes per request over PCIe instead of 8.
+ * Request i occupies bytes [6i, 6i + 6) of one buffer: bytes 0-2 the root, bytes 3-5 the
+ * target, both little-endian; 0xFFFFFF stands for KETOGPU_NODE_NONE.  The format serves a
+ * snapshot with num_nodes <= 0xFFFFFF (ketogpu_snapshot_packed24_ok; a writable snapshot
+ * grows, so every check call tests it again).  The buffer is ketogpu_packed24_bytes(n)
+ * bytes long, 6n rounded up to a multiple of 8, and 8-byte aligned; the padding bytes are
+ * never interpreted and nothing past them is read. */
+size_t ketogpu_packed24_bytes(size_t n);
+/* host code.  NONE becomes 0xFFFFFF; any other id >= 0xFFFFFF fails with KETOGPU_EINVAL
+ * ("request <i> ..."); the padding bytes are written as 0.  out: ketogpu_packed24_bytes(n) */
+int ketogpu_pack24(const uint32_t *roots, const uint32_t *targets, size_t n, void *out);
+/* host code, the inverse (0xFFFFFF becomes KETOGPU_NODE_NONE) */
+int ketogpu_unpack24(const void *packed, size_t n, uint32_t *roots, uint32_t *targets);
+/* 1: the snapshot's ids fit the format now, 0: they do not (or s is NULL) */
+int ketogpu_snapshot_packed24_ok(const ketogpu_snapshot *s);
+/* ketogpu_check_ids over a packed24 buffer: the same bits and flags, an id outside the
+ * snapshot fails the call with KETOGPU_EINVAL and the request's index, flagged_bits may be
+ * NULL.  Also KETOGPU_EINVAL: a buffer that is not 8-byte aligned, a snapshot with more than
+ * 0xFFFFFF nodes (the message says which).  With plan label and a buffer of
+ * ketogpu_host_alloc (or other mapped pinned memory) the first stage reads the packed bytes
+ * in place; every other plan and memory kind expands them into u32 arrays in HBM first
+ * (pageable memory: after one DMA copy of the packed bytes). */
+int ketogpu_check_ids_packed24(ketogpu_engine *e, const void *packed, size_t n, uint64_t *allowed_bits,
+                               uint64_t *flagged_bits);
+/* how the engine's last check call received its requests: 0 = u32 arrays; 1 = packed24,
+ * expanded into HBM ahead of the first stage; 2 = packed24, read in place by the first
+ * stage.  (An accessor of its own: ketogpu_run_stats keeps its layout.) */
+int ketogpu_engine_last_request_path(const ketogpu_engine *e, int32_t *path);
+
 /* Pinned host memory (hipHostMalloc) for request and result arrays.  A batch whose
  * roots/targets live here is copied by DMA at full PCIe rate; the cgo micro-batcher
  *  fills such a buffer in place instead of a Go slice, which it has to
@@ -380,6 +412,10 @@ size_t ketogpu_multi_size(const ketogpu_multi *m);
 ketogpu_engine *ketogpu_multi_engine(ketogpu_multi *m, size_t i);
 int ketogpu_multi_check_ids(ketogpu_multi *m, const uint32_t *roots, const uint32_t *targets, size_t n,
                             uint64_t *allowed_bits, uint64_t *flagged_bits);
+/* the same split over a packed24 buffer (ketogpu_check_ids_packed24): a range begins at a
+ * multiple of 64 requests, 384 bytes, so every device's part keeps the 8-byte alignment */
+int ketogpu_multi_check_ids_packed24(ketogpu_multi *m, const void *packed, size_t n, uint64_t *allowed_bits,
+                                     uint64_t *flagged_bits);
 /* requests [*begin, *end) of part i when n requests are split into `parts` ranges */
 void ketogpu_multi_range(size_t n, size_t parts, size_t i, size_t *begin, size_t *end);
 

@@ -334,6 +334,12 @@ SIGNATURES = {
     "ketogpu_engine_set_events": (C.c_int, [vp, C.c_int]),
     "ketogpu_check": (C.c_int, [vp, C.POINTER(CheckRequest), sz, vp, vp]),
     "ketogpu_check_ids": (C.c_int, [vp, vp, vp, sz, vp, vp]),
+    "ketogpu_packed24_bytes": (sz, [sz]),
+    "ketogpu_pack24": (C.c_int, [vp, vp, sz, vp]),
+    "ketogpu_unpack24": (C.c_int, [vp, sz, vp, vp]),
+    "ketogpu_snapshot_packed24_ok": (C.c_int, [vp]),
+    "ketogpu_check_ids_packed24": (C.c_int, [vp, vp, sz, vp, vp]),
+    "ketogpu_engine_last_request_path": (C.c_int, [vp, C.POINTER(i32)]),
     "ketogpu_queries_upload": (C.c_int, [vp, vp, vp, sz, C.POINTER(vp)]),
     "ketogpu_queries_run": (C.c_int, [vp, vp]),
     "ketogpu_queries_run_async": (C.c_int, [vp, vp, C.POINTER(C.c_int)]),
@@ -357,6 +363,7 @@ SIGNATURES = {
     "ketogpu_multi_size": (sz, [vp]),
     "ketogpu_multi_engine": (vp, [vp, sz]),
     "ketogpu_multi_check_ids": (C.c_int, [vp, vp, vp, sz, vp, vp]),
+    "ketogpu_multi_check_ids_packed24": (C.c_int, [vp, vp, sz, vp, vp]),
     "ketogpu_multi_range": (None, [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]),
     "ketogpu_shard_builder_new": (C.c_int, [C.POINTER(Namespace), sz, C.POINTER(ShardOpts), C.POINTER(vp)]),
     "ketogpu_shard_builder_append": (C.c_int, [vp, C.POINTER(RowBatch)]),

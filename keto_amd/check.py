@@ -99,6 +99,28 @@ class Engine:
         """the C call on caller-owned (e.g. pinned) buffers, no conversions (benchmarks)"""
         L.check(self.L.ketogpu_check_ids(self.h, roots_ptr, targets_ptr, n, allowed_ptr, flagged_ptr))
 
+    def check_ids_packed(self, packed, n, with_flags=False):
+        """check_ids over a packed24 buffer (pack24): 6 bytes per request instead of 8"""
+        packed = _packed_array(packed, n)
+        words = max((n + 63) // 64, 1)
+        ab = np.zeros(words, dtype=np.uint64)
+        fb = np.zeros(words, dtype=np.uint64)
+        L.check(self.L.ketogpu_check_ids_packed24(self.h, packed.ctypes.data, n, ab.ctypes.data, fb.ctypes.data))
+        allowed = unpack_bits(ab, n)
+        return (allowed, unpack_bits(fb, n)) if with_flags else allowed
+
+    def check_ids_packed_raw(self, ptr, n, allowed_ptr, flagged_ptr=None):
+        """the C call on caller-owned buffers (a PinnedBuffer(nbytes, np.uint8) of packed24
+        requests is read in place by plan label's first stage), no conversions"""
+        L.check(self.L.ketogpu_check_ids_packed24(self.h, ptr, n, allowed_ptr, flagged_ptr))
+
+    def last_request_path(self):
+        """how the last check call received its requests: 0 = u32 arrays, 1 = packed24
+        expanded into HBM ahead of the first stage, 2 = packed24 read in place by it"""
+        p = C.c_int32()
+        L.check(self.L.ketogpu_engine_last_request_path(self.h, C.byref(p)))
+        return p.value
+
     def upload(self, roots, targets):
         return DeviceQueries(self, roots, targets)
 
@@ -216,6 +238,19 @@ class MultiEngine:
         """the C call on caller-owned (e.g. pinned) buffers, no conversions (benchmarks)"""
         L.check(self.L.ketogpu_multi_check_ids(self.h, roots_ptr, targets_ptr, n, allowed_ptr, flagged_ptr))
 
+    def check_ids_packed(self, packed, n, with_flags=False):
+        packed = _packed_array(packed, n)
+        words = max((n + 63) // 64, 1)
+        ab = np.zeros(words, dtype=np.uint64)
+        fb = np.zeros(words, dtype=np.uint64)
+        L.check(self.L.ketogpu_multi_check_ids_packed24(self.h, packed.ctypes.data, n, ab.ctypes.data,
+                                                        fb.ctypes.data))
+        allowed = unpack_bits(ab, n)
+        return (allowed, unpack_bits(fb, n)) if with_flags else allowed
+
+    def check_ids_packed_raw(self, ptr, n, allowed_ptr, flagged_ptr=None):
+        L.check(self.L.ketogpu_multi_check_ids_packed24(self.h, ptr, n, allowed_ptr, flagged_ptr))
+
     def last_stats(self, i=0):
         return self.engine(i).last_stats()
 
@@ -233,6 +268,40 @@ class MultiEngine:
 
     def __del__(self):
         self.close()
+
+
+def packed24_bytes(n):
+    """bytes of a packed24 buffer of n requests: 6n rounded up to a multiple of 8"""
+    return L.lib().ketogpu_packed24_bytes(n)
+
+
+def pack24(roots, targets):
+    """u32 ids -> the packed 24-bit request format (ketogpu_pack24): 6 bytes per request,
+    root then target, little-endian, NONE as 0xFFFFFF; a uint8 array of packed24_bytes(n)"""
+    roots = np.ascontiguousarray(roots, dtype=np.uint32)
+    targets = np.ascontiguousarray(targets, dtype=np.uint32)
+    if len(roots) != len(targets):
+        raise ValueError("roots and targets differ in length")
+    # (backed by uint64 words: the format asks for an 8-byte aligned buffer)
+    out = np.zeros(max(packed24_bytes(len(roots)) // 8, 1), dtype=np.uint64).view(np.uint8)
+    L.check(L.lib().ketogpu_pack24(roots.ctypes.data, targets.ctypes.data, len(roots), out.ctypes.data))
+    return out[:packed24_bytes(len(roots))]
+
+
+def unpack24(packed, n):
+    """the inverse of pack24 -> (roots, targets)"""
+    packed = _packed_array(packed, n)
+    roots = np.empty(n, dtype=np.uint32)
+    targets = np.empty(n, dtype=np.uint32)
+    L.check(L.lib().ketogpu_unpack24(packed.ctypes.data, n, roots.ctypes.data, targets.ctypes.data))
+    return roots, targets
+
+
+def _packed_array(packed, n):
+    packed = np.ascontiguousarray(packed, dtype=np.uint8)
+    if len(packed) < packed24_bytes(n):
+        raise ValueError(f"{n} packed24 requests need {packed24_bytes(n)} bytes, got {len(packed)}")
+    return packed
 
 
 def unpack_bits(words, n):

@@ -2848,6 +2848,69 @@ __global__ __launch_bounds__(256) void label_host_kernel(DevGraph g, LabelGraph 
     label_unit<HS, HP>(sh[wave], L, rk, tk, allowed, unit, R, F, stats);
 }
 
+// 64 packed24 requests (ketogpu_check_ids_packed24: 6 bytes each, root then target, three
+// bytes little-endian, 0xFFFFFF = NONE) decoded by one wave: lanes 0-47 read the 384 bytes as
+// 8-byte words w0 .. w0 + 47 of `src` in one wave instruction (words at or past `nwords`, the
+// buffer's ketogpu_packed24_bytes(n) / 8, are not read), exchange them through `raw` (96 LDS
+// words of this wave's own, dword accesses only) and lane j returns request j's ids
+__device__ __forceinline__ void packed24_decode(uint32_t *raw, const uint64_t *src, uint64_t w0, uint64_t nwords,
+                                                uint32_t lane, uint32_t &r, uint32_t &t) {
+    if (lane < 48) {
+        const uint64_t w = w0 + lane < nwords ? src[w0 + lane] : 0ull;
+        *reinterpret_cast<uint2 *>(raw + 2 * lane) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+    }
+    wave_sync();
+    // request j: bytes [6j, 6j + 6) = words 3j/2 and 3j/2 + 1 (<= 95), from bit 16 (j & 1)
+    const uint32_t k = (3 * lane) >> 1;
+    const uint64_t v = ((uint64_t)raw[k + 1] << 32 | raw[k]) >> ((lane & 1) * 16);
+    r = (uint32_t)v & 0xFFFFFFu;
+    t = (uint32_t)(v >> 24) & 0xFFFFFFu;
+    if (r == 0xFFFFFFu) r = KETOGPU_NODE_NONE;
+    if (t == 0xFFFFFFu) t = KETOGPU_NODE_NONE;
+}
+
+// label_host_kernel for packed24 requests: wave 0 reads the workgroup's 64 requests as 384
+// contiguous bytes in ONE wave instruction of 8-byte loads (the u32 arrays take two reads of
+// 256 bytes), decodes and validates them as host_unit_requests does, one request per lane,
+// stores the u32 ids in HBM for the later stages and hands them over in rq (which first
+// serves as the decode's exchange words)
+template <int HS, int HP>
+__global__ __launch_bounds__(256) void label_host_packed_kernel(DevGraph g, LabelGraph L, const uint64_t *hp,
+                                                                uint32_t *dr, uint32_t *dt, uint64_t n,
+                                                                uint64_t *allowed, LabelRest R, LabelRest F,
+                                                                unsigned long long *stats,
+                                                                unsigned long long *first_bad) {
+    __shared__ LabelShared<HS, HP> sh[4];
+    __shared__ uint32_t rq[2][64];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    label_clear_next(R, F);
+    if (wave == 0) {
+        uint32_t r, t;
+        packed24_decode(&rq[0][0], hp, (uint64_t)blockIdx.x * 48, (6 * n + 7) / 8, lane, r, t);
+        const uint64_t c = (uint64_t)blockIdx.x * 64 + lane;
+        if (c < n) {
+            if ((r != KETOGPU_NODE_NONE && r >= g.Nx) || (t != KETOGPU_NODE_NONE && t >= g.N)) {
+                atomicMin(first_bad, (unsigned long long)c);
+                r = t = KETOGPU_NODE_NONE;
+            }
+            dr[c] = r;
+            dt[c] = t;
+        } else {
+            r = t = KETOGPU_NODE_NONE;
+        }
+        wave_sync();  // every lane has read its exchange words
+        rq[0][lane] = r;
+        rq[1][lane] = t;
+    }
+    __syncthreads();
+    const uint64_t units = (n + 15) / 16;
+    const uint64_t unit = (uint64_t)blockIdx.x * 4 + wave;
+    if (unit >= units) return;  // (a whole wave: no barrier follows)
+    const uint32_t rk = lane < 16 ? rq[0][16 * wave + lane] : KETOGPU_NODE_NONE;
+    const uint32_t tk = lane < 16 ? rq[1][16 * wave + lane] : KETOGPU_NODE_NONE;
+    label_unit<HS, HP>(sh[wave], L, rk, tk, allowed, unit, R, F, stats);
+}
+
 // The dense second pass over the requests the first stage's heads did not settle (F: two
 // records per request carrying both counts and overflow starts): gathered 16 to a wave,
 // four lanes per request, persistent.  It answers from the whole lists: the landmark
@@ -3871,6 +3934,29 @@ __global__ __launch_bounds__(kBlock) void load_kernel(const uint32_t *hr, const 
     }
 }
 
+// packed24 requests (ketogpu_check_ids_packed24) expanded into the u32 arrays every first
+// stage reads, validated as validate_kernel does: a wave takes 64 requests (packed24_decode)
+// and writes their ids as coalesced u32.  src: the packed bytes in HBM (one DMA copy of 6 B
+// per request) or the device's view of a pinned buffer.
+__global__ __launch_bounds__(kBlock) void unpack24_kernel(const uint64_t *src, uint64_t n, uint32_t *dr, uint32_t *dt,
+                                                          uint32_t Nx, uint32_t N, unsigned long long *first_bad) {
+    static_assert(kBlock % 64 == 0, "whole waves");
+    __shared__ uint32_t raw[kBlock / 64][96];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t wv = (uint64_t)blockIdx.x * (kBlock / 64) + wave;  // the wave's 64 requests
+    if (wv * 64 >= n) return;                                          // (a whole wave: no barrier follows)
+    uint32_t r, t;
+    packed24_decode(raw[wave], src, wv * 48, (6 * n + 7) / 8, lane, r, t);
+    const uint64_t c = wv * 64 + lane;
+    if (c >= n) return;
+    if ((r != KETOGPU_NODE_NONE && r >= Nx) || (t != KETOGPU_NODE_NONE && t >= N)) {
+        atomicMin(first_bad, (unsigned long long)c);
+        r = t = KETOGPU_NODE_NONE;
+    }
+    dr[c] = r;
+    dt[c] = t;
+}
+
 // The run's results in one launch into pinned host memory: result words, flag words (when
 // wanted) and the first invalid request index — instead of one DMA copy each.
 // out_bits (may be null): the result words go to the caller's own pinned buffer instead
@@ -4387,6 +4473,7 @@ struct Batch {
 struct HostSrc {
     const uint32_t *roots, *targets;
     bool mapped;
+    const uint8_t *packed = nullptr;  // packed24 requests (mapped; roots / targets unused), null for u32 callers
 };
 
 struct ketogpu_queries {
@@ -4627,6 +4714,15 @@ struct ketogpu_engine {
     }
     // plan label, host batches (4 units per workgroup)
     void launch_label_host(const Batch &q, const HostSrc *src, uint64_t bunits) {
+        if (src->packed) {
+            label_dispatch([&](auto hs, auto hp) {
+                KLAUNCH((label_host_packed_kernel<decltype(hs)::value, decltype(hp)::value>),
+                        dim3((unsigned)((bunits + 3) / 4)), dim3(256), 0, stream, g, lgraph,
+                        (const uint64_t *)src->packed, io->d_roots, io->d_targets, q.n, q.allowed, label_rest(q.n),
+                        label_full(q.n), st.stats, d_bad);
+            });
+            return;
+        }
         label_dispatch([&](auto hs, auto hp) {
             KLAUNCH((label_host_kernel<decltype(hs)::value, decltype(hp)::value>), dim3((unsigned)((bunits + 3) / 4)),
                     dim3(256), 0, stream, g, lgraph, src->roots, src->targets, io->d_roots, io->d_targets, q.n,
@@ -4856,6 +4952,10 @@ struct ketogpu_engine {
     // stream for the chunked request upload and a second compute stream
     ketogpu_queries *io = nullptr;
     uint64_t io_cap = 0;
+    uint64_t *d_packed = nullptr;  // packed24 batches from memory the device cannot read in place
+    uint64_t packed_cap = 0;       // its bytes
+    // how the last check call received its requests (ketogpu_engine_last_request_path)
+    int32_t request_path = 0;
     hipStream_t copy_stream = nullptr, stream2 = nullptr;
     unsigned long long *d_bad = nullptr;  // smallest request index with an id outside the snapshot
     uint64_t pipe_chunk = 1 << 18;        // requests per pipelined chunk (KETOGPU_PIPE_CHUNK)
@@ -5187,6 +5287,7 @@ struct ketogpu_engine {
         if (h_ctr) (void)hipHostFree(h_ctr);
         if (h_res) (void)hipHostFree(h_res);
         delete io;
+        if (d_packed) (void)hipFree(d_packed);
         for (hipStream_t x : {copy_stream, stream2})
             if (x) (void)hipStreamDestroy(x);
         if (stream) (void)hipStreamDestroy(stream);
@@ -6651,7 +6752,7 @@ struct ketogpu_engine {
         ensure_io(n);
         ketogpu_queries &q = *io;
         q.n = n;
-        const uint64_t words = (n + 63) / 64;
+        request_path = 0;
         emit_req = EmitReq{};
         clear_bad = nullptr;
         const bool bidi_ok = n && use_units && !wave_u && (use_v2 || use_lite) && use_bidi && !(trials_left && n >= kTrialMin);
@@ -6681,29 +6782,88 @@ struct ketogpu_engine {
             run(q);
         } else {
             const HostSrc src{mapped ? dr : roots, mapped ? dt : targets, mapped};
-            ensure_res(2 * words + 1);
-            clear_bad = d_bad;  // reset by the run's clear launch
-            // results, flags and the validation verdict in one launch with the statistics
-            // result words straight into the caller's buffer when it is a ketogpu_host_alloc
-            // buffer (no host copy after the call)
-            uint64_t *direct_bits = allowed ? (uint64_t *)host_view(allowed, device, false) : nullptr;
-            emit_req = EmitReq{q.d_allowed, flagged ? q.d_flags : nullptr, words, d_bad, h_res, direct_bits};
-            run_once(q, &src, [&] {
-                if (emit_req.out) {  // not taken by the bidi cascade's tail
-                    KLAUNCH(emit_kernel, dim3((unsigned)std::min<uint64_t>(blocks_for(2 * words + 1), 256)),
-                            dim3(kBlock), 0, stream, q.d_allowed, flagged ? q.d_flags : nullptr, words, d_bad, h_res,
-                            direct_bits);
-                    emit_req = EmitReq{};
-                }
-            });
-            // the staged words were final unless requests went on to the global path
-            if (!last.spilled_requests) {
-                const uint64_t nf = flagged ? words : 0;
-                if (allowed && !direct_bits) memcpy(allowed, h_res, words * 8);
-                if (flagged) memcpy(flagged, h_res + words, words * 8);
-                check_bad(h_res[words + nf]);
-                return;
+            if (run_host_src(q, src, allowed, flagged)) return;
+        }
+        HIP_CHECK(hipMemcpyAsync(h_ctr + 40, d_bad, 8, hipMemcpyDeviceToHost, stream));
+        download(q, allowed, flagged);  // synchronizes
+        check_bad(h_ctr[40]);
+    }
+
+    // check_host's pipelined call over requests still on the host (src); true: results,
+    // flags and the validation verdict are delivered, false: they are still in HBM
+    bool run_host_src(ketogpu_queries &q, const HostSrc &src, uint64_t *allowed, uint64_t *flagged) {
+        const uint64_t words = (q.n + 63) / 64;
+        ensure_res(2 * words + 1);
+        clear_bad = d_bad;  // reset by the run's clear launch
+        // results, flags and the validation verdict in one launch with the statistics
+        // result words straight into the caller's buffer when it is a ketogpu_host_alloc
+        // buffer (no host copy after the call)
+        uint64_t *direct_bits = allowed ? (uint64_t *)host_view(allowed, device, false) : nullptr;
+        emit_req = EmitReq{q.d_allowed, flagged ? q.d_flags : nullptr, words, d_bad, h_res, direct_bits};
+        run_once(q, &src, [&] {
+            if (emit_req.out) {  // not taken by the bidi cascade's tail
+                KLAUNCH(emit_kernel, dim3((unsigned)std::min<uint64_t>(blocks_for(2 * words + 1), 256)),
+                        dim3(kBlock), 0, stream, q.d_allowed, flagged ? q.d_flags : nullptr, words, d_bad, h_res,
+                        direct_bits);
+                emit_req = EmitReq{};
             }
+        });
+        // the staged words were final unless requests went on to the global path
+        if (!last.spilled_requests) {
+            const uint64_t nf = flagged ? words : 0;
+            if (allowed && !direct_bits) memcpy(allowed, h_res, words * 8);
+            if (flagged) memcpy(flagged, h_res + words, words * 8);
+            check_bad(h_res[words + nf]);
+            return true;
+        }
+        return false;
+    }
+
+    // the packed bytes of a packed24 batch in HBM (pageable or unmapped callers: one DMA copy)
+    void ensure_packed(uint64_t bytes) {
+        if (d_packed && bytes <= packed_cap) return;
+        if (d_packed) (void)hipFree(d_packed);
+        d_packed = nullptr;
+        packed_cap = std::max<uint64_t>(bytes, 6 << 16);
+        d_packed = dalloc<uint64_t>(packed_cap / 8);
+    }
+
+    // check_host over packed24 requests (ketogpu_check_ids_packed24; `packed` is 8-byte
+    // aligned and ketogpu_packed24_bytes(n) long).  Plan label with a mapped buffer and the
+    // direct mode (where the u32 call launches label_host_kernel): the first stage reads the
+    // packed bytes in place (label_host_packed_kernel).  Everything else: unpack24_kernel
+    // expands them into the u32 arrays in HBM, from the mapped view or from a staging buffer
+    // filled by one DMA copy, and the batch runs as a device-resident one.
+    void check_host_packed(const uint8_t *packed, uint64_t n, uint64_t *allowed, uint64_t *flagged) {
+        HIP_CHECK(hipSetDevice(device));
+        if (g.N > 0xFFFFFFu)
+            throw Error(KETOGPU_EINVAL, "packed24 requests: the snapshot has " + std::to_string(g.N) +
+                                            " nodes, more than 24-bit ids address");
+        ensure_io(n);
+        ketogpu_queries &q = *io;
+        q.n = n;
+        emit_req = EmitReq{};
+        clear_bad = nullptr;
+        const bool bidi_ok = n && use_units && !wave_u && (use_v2 || use_lite) && use_bidi && !(trials_left && n >= kTrialMin);
+        const uint8_t *dv = n ? (const uint8_t *)host_view(packed, device, n >= 2 * pipe_chunk) : nullptr;
+        if (bidi_ok && dv && pipe_direct && bidi_cfg.lite == 3) {
+            request_path = 2;
+            HostSrc src{nullptr, nullptr, true};
+            src.packed = dv;
+            if (run_host_src(q, src, allowed, flagged)) return;
+        } else {
+            request_path = 1;
+            HIP_CHECK(hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), stream));
+            if (n) {
+                const uint64_t bytes = (6 * n + 7) / 8 * 8;
+                if (!dv) {
+                    ensure_packed(bytes);
+                    HIP_CHECK(hipMemcpyAsync(d_packed, packed, bytes, hipMemcpyHostToDevice, stream));
+                }
+                KLAUNCH(unpack24_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream,
+                        dv ? (const uint64_t *)dv : d_packed, n, q.d_roots, q.d_targets, g.Nx, g.N, d_bad);
+            }
+            run(q);
         }
         HIP_CHECK(hipMemcpyAsync(h_ctr + 40, d_bad, 8, hipMemcpyDeviceToHost, stream));
         download(q, allowed, flagged);  // synchronizes
@@ -6713,6 +6873,7 @@ struct ketogpu_engine {
     // validate = false: ids built by the library itself (ketogpu_check, dynamic roots)
     ketogpu_queries *upload(const uint32_t *roots, const uint32_t *targets, uint64_t n, bool validate = true) {
         HIP_CHECK(hipSetDevice(device));
+        request_path = 0;
         auto q = std::make_unique<ketogpu_queries>();
         q->n = n;
         uint64_t words = std::max<uint64_t>((n + 63) / 64, 1);
@@ -6900,6 +7061,27 @@ int ketogpu_check_ids(ketogpu_engine *e, const uint32_t *roots, const uint32_t *
     e->sync();
     e->check_host(roots, targets, n, allowed_bits, flagged_bits);
     API_END
+}
+
+int ketogpu_check_ids_packed24(ketogpu_engine *e, const void *packed, size_t n, uint64_t *allowed_bits,
+                               uint64_t *flagged_bits) {
+    API_BEGIN
+    if (!e || (n && (!packed || !allowed_bits))) throw Error(KETOGPU_EINVAL, "null argument");
+    if ((uintptr_t)packed % 8) throw Error(KETOGPU_EINVAL, "packed24 requests: the buffer is not 8-byte aligned");
+    std::shared_lock<std::shared_mutex> rd(e->snap->mu);
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->sync();
+    e->check_host_packed(static_cast<const uint8_t *>(packed), n, allowed_bits, flagged_bits);
+    API_END
+}
+
+int ketogpu_engine_last_request_path(const ketogpu_engine *e, int32_t *path) {
+    if (!e || !path) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *path = e->request_path;
+    return KETOGPU_OK;
 }
 
 int ketogpu_host_alloc(size_t bytes, void **out) {

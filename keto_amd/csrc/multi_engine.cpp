@@ -32,6 +32,7 @@ struct ketogpu_multi {
     bool stop = false;
     // the current job
     const uint32_t *roots = nullptr, *targets = nullptr;
+    const uint8_t *packed = nullptr;  // packed24 requests instead of roots / targets
     size_t n = 0;
     uint64_t *allowed = nullptr, *flagged = nullptr;
     std::vector<int> rc;
@@ -63,8 +64,11 @@ struct ketogpu_multi {
             int r = KETOGPU_OK;
             std::string msg;
             if (e > b) {
-                r = ketogpu_check_ids(eng[i], roots + b, targets + b, e - b, allowed + b / 64,
-                                      flagged ? flagged + b / 64 : nullptr);
+                // (a range begins at a multiple of 64 requests = 384 bytes: still 8-byte aligned)
+                r = packed ? ketogpu_check_ids_packed24(eng[i], packed + 6 * b, e - b, allowed + b / 64,
+                                                        flagged ? flagged + b / 64 : nullptr)
+                           : ketogpu_check_ids(eng[i], roots + b, targets + b, e - b, allowed + b / 64,
+                                               flagged ? flagged + b / 64 : nullptr);
                 if (r) msg = ketogpu_last_error();  // thread-local: read on this thread
             }
             {
@@ -137,17 +141,15 @@ ketogpu_engine *ketogpu_multi_engine(ketogpu_multi *m, size_t i) {
     return m && i < m->eng.size() ? m->eng[i] : nullptr;
 }
 
-int ketogpu_multi_check_ids(ketogpu_multi *m, const uint32_t *roots, const uint32_t *targets, size_t n,
-                            uint64_t *allowed_bits, uint64_t *flagged_bits) {
-    if (!m || (n && (!roots || !targets || !allowed_bits))) {
-        set_last_error("null argument");
-        return KETOGPU_EINVAL;
-    }
+// one batch over every device: u32 arrays, or packed24 bytes when `packed` is set
+static int multi_run(ketogpu_multi *m, const uint32_t *roots, const uint32_t *targets, const uint8_t *packed, size_t n,
+                     uint64_t *allowed_bits, uint64_t *flagged_bits) {
     std::lock_guard<std::mutex> call(m->call_mu);
     {
         std::lock_guard<std::mutex> lk(m->mu);
         m->roots = roots;
         m->targets = targets;
+        m->packed = packed;
         m->n = n;
         m->allowed = allowed_bits;
         m->flagged = flagged_bits;
@@ -166,6 +168,29 @@ int ketogpu_multi_check_ids(ketogpu_multi *m, const uint32_t *roots, const uint3
             return m->rc[i];
         }
     return KETOGPU_OK;
+}
+
+int ketogpu_multi_check_ids(ketogpu_multi *m, const uint32_t *roots, const uint32_t *targets, size_t n,
+                            uint64_t *allowed_bits, uint64_t *flagged_bits) {
+    if (!m || (n && (!roots || !targets || !allowed_bits))) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    return multi_run(m, roots, targets, nullptr, n, allowed_bits, flagged_bits);
+}
+
+int ketogpu_multi_check_ids_packed24(ketogpu_multi *m, const void *packed, size_t n, uint64_t *allowed_bits,
+                                     uint64_t *flagged_bits) {
+    if (!m || (n && (!packed || !allowed_bits))) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    if ((uintptr_t)packed % 8) {
+        set_last_error("packed24 requests: the buffer is not 8-byte aligned");
+        return KETOGPU_EINVAL;
+    }
+    if (!n) return KETOGPU_OK;
+    return multi_run(m, nullptr, nullptr, static_cast<const uint8_t *>(packed), n, allowed_bits, flagged_bits);
 }
 
 }  // extern "C"

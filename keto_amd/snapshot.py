@@ -170,6 +170,11 @@ class Snapshot:
         L.check(self.L.ketogpu_snapshot_stats_get(self.h, C.byref(st)))
         return st.as_dict()
 
+    def packed24_ok(self):
+        """every node id fits the packed 24-bit request format (check.pack24) now; a writable
+        snapshot grows, so ask again after writes"""
+        return bool(self.L.ketogpu_snapshot_packed24_ok(self.h))
+
     def graph(self):
         """numpy copies of the device graph (ketogpu_snapshot_graph)"""
         v = L.GraphView()

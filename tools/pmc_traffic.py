@@ -26,6 +26,7 @@ FAMILIES = [
     ("bidi_host_kernel (host batches)", r"bidi_host_kernel"),
     # plan label: closure labels (one intersection per request)
     ("label_host_kernel (host batches)", r"label_host_kernel"),
+    ("label_host_packed_kernel (host batches, packed24 requests)", r"label_host_packed_kernel"),
     ("label_rest_kernel (second stage)", r"label_rest_kernel"),
     ("label_full_kernel (overflow lists)", r"label_full_kernel"),
     ("label_kernel", r"\blabel_kernel"),
