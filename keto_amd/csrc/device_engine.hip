@@ -2924,33 +2924,24 @@ __global__ __launch_bounds__(256) void label_host_packed_kernel(DevGraph g, Labe
 // otherwise be searched in global memory (config #3 shape: 7.1 vs 7.6e9 pipelined;
 // profiles/r06/stage/)
 __host__ __device__ constexpr uint32_t full_stage(int HS, int HP) { return HS >= 64 || HP >= 64 ? 256u : 128u; }
-// Workgroup 0 also totals both lists' shard counts for the host (totals[0]: the rest list,
-// totals[1]: this list), so the rest stage can be launched only when it has requests.
-// Lean resident calls (plan label, timing events off, KETOGPU_LABEL_FUSE=1): the first
-// stage and this pass run without statistics atomics (stats == nullptr: the statistics are
-// diagnostics, collected by the same calls with events on), and workgroup 0 writes the two
-// list totals straight into the host-mapped mirror (`mirror`: the words stats_reduce_kernel
-// would write — zero statistics, spill counters {rest total, 0 ... 0, full total}), so the
-// call needs no statistics launch and, after a call without rest requests, no clear.
-template <int HS, int HP>
-__global__ __launch_bounds__(64) void label_full_kernel(LabelGraph L, uint64_t *allowed, LabelRest R, LabelRest F,
-                                                        unsigned int *total_rest, unsigned int *total_full,
-                                                        unsigned long long *stats, unsigned long long *mirror) {
-    constexpr uint32_t kFullStage = full_stage(HS, HP);
-    __shared__ alignas(16) uint32_t stage[16][kFullStage];
+
+// the pass's persistent loop: gathered units first, first + stride, ... of the list F (c: this
+// lane's shard count), 16 requests per wave and four lanes per request; `stage`: 16 rows of
+// kStage words in LDS; kPre walked entries per lane are fetched together and kFly 16-byte
+// staging loads per lane are in flight at once (registers: kPre + 4 kFly).  Returns the
+// entries read (this lane's requests).
+template <int HS, int HP, uint32_t kStage, int kPre, int kFly>
+__device__ __forceinline__ uint64_t label_dense_units(uint32_t *stage, const LabelGraph &L, uint64_t *allowed,
+                                                      const LabelRest &F, const uint32_t c, const uint32_t first_u,
+                                                      const uint32_t stride) {
+    static_assert(kStage % 4 == 0, "16-byte aligned rows");
     const uint32_t lane = threadIdx.x, q = lane >> 2, sub = lane & 3;
-    const uint32_t c = F.count[lane * kRestStride];
     const uint32_t nu = (c + 15) / 16;
     const uint32_t incl = wave_incl_sum_u32(nu);
     const uint64_t units = (uint64_t)__builtin_amdgcn_readlane((int)incl, 63);
-    if (blockIdx.x == 0) {
-        const uint32_t tr = wave_sum_all(R.count[lane * kRestStride]), tf = wave_sum_all(c);
-        if (lane == 0) *total_rest = tr, *total_full = tf;
-        if (mirror && lane < 12)  // u32 spill counters at words 8..11: [0] rest total, [7] full total
-            mirror[lane] = lane == 8 ? (unsigned long long)tr : lane == 11 ? (unsigned long long)tf << 32 : 0ull;
-    }
+    uint32_t *row = stage + q * kStage;
     uint64_t ent = 0;
-    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
+    for (uint64_t u = first_u; u < units; u += stride) {
         const uint32_t shard = (uint32_t)__builtin_ctzll(__ballot(incl > u));
         const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)(incl - nu), (int)shard);
         const uint32_t cs = (uint32_t)__builtin_amdgcn_readlane((int)c, (int)shard);
@@ -2975,30 +2966,33 @@ __global__ __launch_bounds__(64) void label_full_kernel(LabelGraph L, uint64_t *
         const uint32_t *Lg = walk_p ? Sg : Pg, *W = walk_p ? Pg : Sg;
         // (16-byte units: an overflow region is 16-word aligned, a head's entries start 16
         // bytes into a 32-byte aligned head and are padded to a multiple of 4 words)
-        {  // every staging load in flight before the LDS stores (a quad covers kFullStage words)
-            constexpr int kSt = kFullStage / 16;  // 16-byte loads per lane
-            const bool st = valid && nl <= kFullStage;
-            uint4 v[kSt];
+        {  // kFly staging loads in flight before their LDS stores (a quad covers kStage words)
+            constexpr int kSt = (kStage / 4 + 3) / 4;  // 16-byte loads per lane
+            const bool st = valid && nl <= kStage;
 #pragma unroll
-            for (int k = 0; k < kSt; k++) {
-                const uint32_t i = sub + 4 * k;
-                v[k] = st && i * 4 < nl ? reinterpret_cast<const uint4 *>(Lg)[i] : make_uint4(0u, 0u, 0u, 0u);
-            }
+            for (int k0 = 0; k0 < kSt; k0 += kFly) {
+                uint4 v[kFly];
 #pragma unroll
-            for (int k = 0; k < kSt; k++) {
-                const uint32_t i = sub + 4 * k;
-                if (st && i * 4 < nl) reinterpret_cast<uint4 *>(stage[q])[i] = v[k];
+                for (int k = 0; k < kFly; k++) {
+                    const uint32_t i = sub + 4 * (k0 + k);
+                    v[k] = k0 + k < kSt && st && i * 4 < nl ? reinterpret_cast<const uint4 *>(Lg)[i]
+                                                            : make_uint4(0u, 0u, 0u, 0u);
+                }
+#pragma unroll
+                for (int k = 0; k < kFly; k++) {
+                    const uint32_t i = sub + 4 * (k0 + k);
+                    if (k0 + k < kSt && st && i * 4 < nl) reinterpret_cast<uint4 *>(row)[i] = v[k];
+                }
             }
         }
-        constexpr int kPre = 16;  // the walked entries this lane takes, fetched together
-        uint32_t wk[kPre];
+        uint32_t wk[kPre];  // the walked entries this lane takes, fetched together
 #pragma unroll
         for (int i = 0; i < kPre; i++) {
             const uint32_t k = sub + 4 * i;
             wk[i] = valid && k < nw ? W[k] : 0u;
         }
         wave_sync();
-        const uint32_t *O = nl <= kFullStage ? stage[q] : Lg;
+        const uint32_t *O = nl <= kStage ? row : Lg;
         bool hit = false;
         if (valid) {
 #pragma unroll
@@ -3016,8 +3010,71 @@ __global__ __launch_bounds__(64) void label_full_kernel(LabelGraph L, uint64_t *
         }
         wave_sync();  // (the LDS rows are rewritten by the next unit)
     }
+    return ent;
+}
+
+// The dense pass as a launch of its own (every non-pipelined call, and a pipelined call's
+// pass that no later launch carried: label_carry_kernel).
+// Workgroup 0 also totals both lists' shard counts for the host (totals[0]: the rest list,
+// totals[1]: this list), so the rest stage can be launched only when it has requests.
+// Lean resident calls (plan label, timing events off, KETOGPU_LABEL_FUSE=1): the first
+// stage and this pass run without statistics atomics (stats == nullptr: the statistics are
+// diagnostics, collected by the same calls with events on), and workgroup 0 writes the two
+// list totals straight into the host-mapped mirror (`mirror`: the words stats_reduce_kernel
+// would write — zero statistics, spill counters {rest total, 0 ... 0, full total}), so the
+// call needs no statistics launch and, after a call without rest requests, no clear.
+template <int HS, int HP>
+__global__ __launch_bounds__(64) void label_full_kernel(LabelGraph L, uint64_t *allowed, LabelRest R, LabelRest F,
+                                                        unsigned int *total_rest, unsigned int *total_full,
+                                                        unsigned long long *stats, unsigned long long *mirror) {
+    constexpr uint32_t kFullStage = full_stage(HS, HP);
+    __shared__ alignas(16) uint32_t stage[16 * kFullStage];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t c = F.count[lane * kRestStride];
+    if (blockIdx.x == 0) {
+        const uint32_t tr = wave_sum_all(R.count[lane * kRestStride]), tf = wave_sum_all(c);
+        if (lane == 0) *total_rest = tr, *total_full = tf;
+        if (mirror && lane < 12)  // u32 spill counters at words 8..11: [0] rest total, [7] full total
+            mirror[lane] = lane == 8 ? (unsigned long long)tr : lane == 11 ? (unsigned long long)tf << 32 : 0ull;
+    }
+    const uint64_t ent =
+        label_dense_units<HS, HP, kFullStage, 16, (int)kFullStage / 16>(stage, L, allowed, F, c, blockIdx.x, gridDim.x);
     const uint32_t e = wave_sum_all((uint32_t)ent);
     if (stats && lane == 0 && e) atomicAdd(&stat_slot(stats)[2], (unsigned long long)e);
+}
+
+// A pipelined lean call's first stage that also carries ANOTHER call's dense pass: the first
+// D workgroups run label_full_kernel's loop over the record set Fd of the previous pipelined
+// call on this stream (complete and visible: that call's first stage was the previous launch
+// on the stream) and OR into that call's result words `allowed_d`; workgroup D + u is unit u
+// of this call's first stage, as in label_kernel.  The dense workgroups come first, so their
+// chains of dependent reads start at once and run under the whole first stage.  They reuse
+// the unit's head images as their stage (16 rows of HS + HP + 8 words, a longer list is
+// searched in global memory) with 4 walked entries and 2 staging loads per lane in flight, so
+// the kernel holds as many workgroups per CU as label_kernel does.
+template <int HS, int HP>
+__global__ __launch_bounds__(64) void label_carry_kernel(LabelGraph L, const uint32_t *roots, const uint32_t *targets,
+                                                         uint64_t n, uint64_t *allowed, LabelRest R, LabelRest F,
+                                                         LabelRest Fd, uint64_t *allowed_d, uint32_t D) {
+    __shared__ LabelShared<HS, HP> sh;
+    static_assert(sizeof(LabelShared<HS, HP>) == 64 * (HS + HP + 8), "the dense role's stage");
+    if (blockIdx.x < D) {  // (a whole workgroup: one wave)
+        label_dense_units<HS, HP, HS + HP + 8, 4, 2>(reinterpret_cast<uint32_t *>(&sh), L, allowed_d, Fd,
+                                                     Fd.count[threadIdx.x * kRestStride], blockIdx.x, D);
+        return;
+    }
+    if (blockIdx.x == D) {  // the next call's list counters, as label_clear_next
+        R.next_count[threadIdx.x * kRestStride] = 0u;
+        F.next_count[threadIdx.x * kRestStride] = 0u;
+    }
+    const uint64_t units = (n + 15) / 16;
+    const uint64_t unit = blockIdx.x - D;
+    uint32_t r, t;
+    bidi_load_rt<16>(unit, units, roots, targets, n, r, t);
+    label_unit<HS, HP>(sh, L, r, t, allowed, unit, R, F, nullptr);
+    // the last result word's 16-bit parts past the last unit (no unit writes them)
+    if (unit + 1 == units && threadIdx.x == 0)
+        for (uint64_t u = units; u < (units + 3) / 4 * 4; u++) reinterpret_cast<uint16_t *>(allowed)[u] = 0;
 }
 
 // the second stage: plan lite's traversal over the requests the labels did not answer
@@ -4491,6 +4548,24 @@ struct ketogpu_queries {
     // its download waits for that call alone
     hipEvent_t done_ev = nullptr;
     bool pending = false;
+    // Deferred dense passes (ketogpu_engine: PendingDense).  A batch has two result-word
+    // arrays: d_allowed is the one its latest call writes (every reader uses it), d_allowed_alt
+    // the one of the call before — a pipelined call swaps them, so the launch that carries the
+    // earlier call's dense pass (atomic ORs into that call's array) may be this batch's next
+    // first stage (plain 16-bit stores into the other array).  `wrote` / `wrote_alt`: the pipe
+    // stream and drain epoch of the last queued call that wrote each array (a call on another
+    // stream orders after that stream).  `pass`: the latest call's dense pass is 0 = done with
+    // the call (or ordered before done_ev), 1 = pending in `eng` (flushed before the results
+    // are read or the batch freed), 2 = carried by a later launch on the call's stream
+    // `last_s` (done_ev is recorded there again before anything waits for it).
+    uint64_t *d_allowed_alt = nullptr;
+    struct Wrote {
+        unsigned s = 0;
+        uint64_t epoch = 0;  // 0: never
+    } wrote, wrote_alt;
+    int pass = 0;
+    unsigned last_s = 0;
+    ketogpu_engine *eng = nullptr;
     Batch batch() const {
         Batch b;
         b.roots = d_roots;
@@ -4507,7 +4582,8 @@ struct ketogpu_queries {
         return b;
     }
     ~ketogpu_queries() {
-        for (void *p : {(void *)d_roots, (void *)d_targets, (void *)d_allowed, (void *)d_flags, (void *)d_dyn_int_off,
+        for (void *p : {(void *)d_roots, (void *)d_targets, (void *)d_allowed, (void *)d_allowed_alt, (void *)d_flags,
+                        (void *)d_dyn_int_off,
                         (void *)d_dyn_full_off, (void *)d_dyn_int, (void *)d_dyn_full, (void *)d_dyn_amb})
             if (p) (void)hipFree(p);
         if (done_ev) (void)hipEventDestroy(done_ev);
@@ -4612,17 +4688,20 @@ struct ketogpu_engine {
     // them: every request but wildcard roots is one intersection)
     bool use_label = false;
     LabelGraph lgraph{};
-    // rest and full lists: kLabelSets sets each of kRestShards counters, one cache line each;
-    // call k uses set k mod kLabelSets and clears set (k + kPipe) mod kLabelSets for call
+    // rest and full lists: kLabelSets sets each of kRestShards counters, one cache line each.
+    // Call k WRITES set k mod kLabelSets and CLEARS set (k + kPipe) mod kLabelSets for call
     // k + kPipe — the next call on the same stream when pipelined calls rotate over kPipe
-    // streams (ketogpu_queries_run_async), so a call's dense pass may still read its counters
-    // while later calls' first stages run
+    // streams (ketogpu_queries_run_async); its launch may also READ set (k - kPipe) mod
+    // kLabelSets, the dense pass of the previous call on its stream carried along
+    // (label_carry_kernel).  Three sets per stream keep the three apart; a set's last reader
+    // (call k + kPipe's launch, or an earlier flush on that stream) is ordered by the stream
+    // before the launch that clears it again (call k + 2 kPipe's)
     // streams pipelined calls rotate over (ketogpu_queries_run_async).  Two: with four, the
     // calls' first stages share the GPU fairly, end together and leave their dense passes to
     // run together with no first stage beside them (0.0754 vs 0.0614 ms per config #2 call,
     // profiles/r06/pipe/)
     static constexpr unsigned kPipe = 2;
-    static constexpr unsigned kLabelSets = 2 * kPipe;
+    static constexpr unsigned kLabelSets = 3 * kPipe;
     unsigned int *rest_counts = nullptr;
     uint64_t label_calls = 0;  // selects the set
     LabelRest label_rest(uint64_t n) {    // this call's rest list over requests [0, n)
@@ -4663,12 +4742,72 @@ struct ketogpu_engine {
     // over the SAME batch never overlap (they write one result array), a call waits for the
     // batch's previous one (its done_ev)
     const ketogpu_queries *pipe_q[kPipe] = {};
+    // Deferred dense passes (KETOGPU_LABEL_DEFER, default on; 0: every queued call launches
+    // its own pass right after its first stage, two launches per call).  A queued call's dense
+    // pass is not launched with it: it stays PENDING on the call's stream (one per stream) and
+    // the next queued call on that stream carries it in its own launch (label_carry_kernel:
+    // the records are complete and visible by stream order, the pass runs under that call's
+    // first stage instead of after its own).  No result is observable without its pass:
+    // flush_dense launches a pending pass as a plain label_full_kernel on its stream before
+    // the batch's results are read (download), before its next call on another stream, before
+    // the batch is freed, before anything rewrites or frees what the pass reads (drain_pipe:
+    // every non-pipelined entry point, a sync with writes to apply, a relabel swap;
+    // ensure_spill's reallocation), before a call that is not queued this way itself (plan
+    // trials, another plan, rest requests possible) and when the engine is destroyed.
+    bool label_defer = [] {
+        const char *e = getenv("KETOGPU_LABEL_DEFER");
+        return !e || atoi(e) != 0;
+    }();
+    // KETOGPU_LABEL_DONE_EVENT: a queued call's completion event.  "demand" (2, the default):
+    // recorded only when something waits for it — a download of the batch, or its next call on
+    // another stream — on the call's stream as it stands then; "record" (0): after every
+    // queued call, the event packet between two launches costs ~6.7 us of stream idle against
+    // none (config #2: 0.0456 -> 0.0424 ms per step); "nofence" (1): recorded after every call
+    // without the system fence (0.0430 ms).  DESIGN.md Kernels 0a
+    int done_mode = [] {
+        const char *e = getenv("KETOGPU_LABEL_DONE_EVENT");
+        return !e ? 2 : !strcmp(e, "record") ? 0 : !strcmp(e, "nofence") ? 1 : 2;
+    }();
+    struct PendingDense {
+        bool on = false;
+        ketogpu_queries *q = nullptr;  // the batch (its `pass` is 1 while this entry holds it)
+        uint64_t *allowed = nullptr;   // the call's result words
+        LabelRest R{}, F{};            // the call's counter sets and records
+    } pend[kPipe];
+    bool carry_call = false;  // this call is queued with its dense pass pending (set per call)
+    unsigned cur_pipe = 0;    // the pipe stream this call runs on (`stream` and pipe_s[cur_pipe] are swapped meanwhile)
+    uint64_t pipe_epoch = 1;  // drains so far + 1: queued work of an earlier epoch is complete
+    hipEvent_t order_ev = nullptr;
+    hipStream_t pstream(unsigned k) const {
+        if (k == cur_pipe) return stream;
+        return k ? pipe_s[k] : pipe_s[cur_pipe];
+    }
+    unsigned dense_grid() const { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(full_prev / 16 + 64, 64), 16384); }
+    void flush_dense(unsigned k) {
+        PendingDense p = pend[k];
+        if (!p.on) return;
+        pend[k] = PendingDense{};
+        label_dispatch([&](auto hs, auto hp) {
+            KLAUNCH((label_full_kernel<decltype(hs)::value, decltype(hp)::value>), dim3(dense_grid()), dim3(64), 0,
+                    pstream(k), lgraph, p.allowed, p.R, p.F, &spill_count[0], &spill_count[7], nullptr, d_hctr + 16);
+        });
+        if (p.q) {  // the batch's results are complete at its event again
+            if (p.q->done_ev) HIP_CHECK(hipEventRecord(p.q->done_ev, pstream(k)));
+            p.q->pass = 0;
+        }
+    }
+    void flush_dense_all() {
+        for (unsigned k = 0; k < kPipe; k++) flush_dense(k);
+    }
+    // every queued call and pending pass complete (a host wait per stream used)
     void drain_pipe() {
+        flush_dense_all();
         for (unsigned k = 0; k < kPipe; k++) {
             pipe_q[k] = nullptr;
-            if (k && pipe_used[k]) HIP_CHECK(hipStreamSynchronize(pipe_s[k]));
+            if (pipe_used[k]) HIP_CHECK(hipStreamSynchronize(pstream(k)));
             pipe_used[k] = false;
         }
+        pipe_epoch++;
     }
     bool pipe_busy() const {
         for (unsigned k = 1; k < kPipe; k++)
@@ -5271,6 +5410,13 @@ struct ketogpu_engine {
         // every stream of the engine drains before anything it may read or write is freed
         // (the chunk pipeline's copies run on copy_stream and its launches on stream2)
         (void)hipSetDevice(device);
+        try {  // pending dense passes run before their records go (their batches outlive the engine)
+            flush_dense_all();
+        } catch (const Error &) {
+        }
+        for (PendingDense &p : pend)
+            if (p.q) p.q->pass = 0, p.q->eng = nullptr;
+        if (order_ev) (void)hipEventDestroy(order_ev);
         for (hipStream_t x : {stream, stream2, copy_stream})
             if (x) (void)hipStreamSynchronize(x);
         for (auto e : ev_pool) (void)hipEventDestroy(e);
@@ -5984,7 +6130,9 @@ struct ketogpu_engine {
     // used as the ping-pong lists of the cascade
     void ensure_spill(uint64_t n) {
         if (n <= spill_cap) return;
-        // (a queued call on either stream may still read the lists: let them finish first)
+        // (a queued call on either stream may still read the lists, and a pending dense pass
+        // reads the records: launch those, then let them all finish)
+        flush_dense_all();
         if (pipe_busy() || pipe_q[0]) HIP_CHECK(hipDeviceSynchronize());
         for (void *p : {(void *)spill_units, (void *)spill_roots, (void *)spill_targets, (void *)spill_allowed,
                         (void *)spill_flags})
@@ -6057,13 +6205,21 @@ struct ketogpu_engine {
         // plan label: the dense pass over the requests with an overflowing list, always (it
         // also totals the rest list for the lazy decision below: spill_count[0]); persistent,
         // its grid from the previous call's count
-        if (bidi_cfg.lite == 3)
+        // (a call queued with its pass pending launches none: carry_call)
+        if (bidi_cfg.lite == 3 && !carry_call)
             label_dispatch([&](auto hs, auto hp) {
-                const unsigned fg = (unsigned)std::min<uint64_t>(std::max<uint64_t>(full_prev / 16 + 64, 64), 16384);
-                KLAUNCH((label_full_kernel<decltype(hs)::value, decltype(hp)::value>), dim3(fg), dim3(64), 0, stream,
-                        lgraph, q.allowed, label_rest(q.n), label_full(q.n), &spill_count[0], &spill_count[7],
+                KLAUNCH((label_full_kernel<decltype(hs)::value, decltype(hp)::value>), dim3(dense_grid()), dim3(64), 0,
+                        stream, lgraph, q.allowed, label_rest(q.n), label_full(q.n), &spill_count[0], &spill_count[7],
                         fused ? nullptr : st.stats + 4 * kStatSlots, fused ? d_hctr + 16 : nullptr);
             });
+        if (carry_call) {  // the pass stays pending on this stream (run_async names its batch)
+            PendingDense &p = pend[cur_pipe];
+            p.on = true;
+            p.q = nullptr;
+            p.allowed = q.allowed;
+            p.R = label_rest(q.n);
+            p.F = label_full(q.n);
+        }
         if (fused && pipelined_req && !trials_left && label_rest_free(q)) {
             // a pipelined lean call (ketogpu_queries_run_async): no request of this batch can
             // be listed for the second stage (label_rest_free), so nothing after the dense pass
@@ -6076,8 +6232,8 @@ struct ketogpu_engine {
             rs.full_requests = full_prev;  // (not read back: the last synchronized call's count)
             label_clean = true;
             label_calls++;
-            rs.push_launches += 2;
-            rs.unit_launches += 2;
+            rs.push_launches += carry_call ? 1 : 2;
+            rs.unit_launches += carry_call ? 1 : 2;
             return 0;
         }
         auto launch_stages = [&](uint64_t prev0) {
@@ -6241,7 +6397,19 @@ struct ketogpu_engine {
                 hipEvent_t a = light ? light_begin : ev(), b = light ? nullptr : ev();
                 if (!light) HIP_CHECK(hipEventRecord(a, stream));
                 const uint64_t bunits = (q.n + bidi_cfg.u - 1) / bidi_cfg.u;
-                if (!src) {
+                if (!src && carry_call) {
+                    // the first stage and, in the same launch, the dense pass pending on this
+                    // stream (the previous queued call's here)
+                    PendingDense p = pend[cur_pipe];
+                    pend[cur_pipe] = PendingDense{};
+                    const unsigned D = p.on ? dense_grid() : 0u;
+                    label_dispatch([&](auto hs, auto hp) {
+                        KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value>),
+                                dim3(D + (unsigned)bunits), dim3(64), lds_pad, stream, lgraph, q.roots, q.targets, q.n,
+                                q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D);
+                    });
+                    if (p.q) p.q->pass = 2;
+                } else if (!src) {
                     launch_bidi(bidi_cfg, (unsigned)bunits, lds_pad, q, nullptr, nullptr, list[0], &spill_count[0],
                                 lean_call ? nullptr : st.stats, stamps);  // (lean: no statistics atomics)
                 } else if (direct) {
@@ -6606,6 +6774,14 @@ struct ketogpu_engine {
         const bool label_resident = !src && use_units && !wave_u && use_bidi && bidi_cfg.lite == 3 && q.n;
         static const bool eager_env = getenv("KETOGPU_CASCADE_EAGER") != nullptr;
         lean_call = label_resident && fuse_reduce && light_events && !eager_env && !cascade_log && stage_prev[0] == 0;
+        // queued with its dense pass pending (bidi_tail returns it `queued` on the same terms).
+        // Any other call launches the pending passes first; so does one whose first stage
+        // would store into the very array the pass on its stream ORs into
+        carry_call = lean_call && label_defer && pipelined_req && !trials_left && label_rest_free(q);
+        if (!carry_call)
+            flush_dense_all();
+        else if (pend[cur_pipe].on && pend[cur_pipe].allowed == q.allowed)
+            flush_dense(cur_pipe);
         const auto h0 = std::chrono::steady_clock::now();
         light_begin = nullptr;
         if (light_events && (src || (use_units && !wave_u && use_bidi && q.n && bidi_cfg.lite == 3))) {
@@ -6880,6 +7056,7 @@ struct ketogpu_engine {
         q->d_roots = dalloc<uint32_t>(n);
         q->d_targets = dalloc<uint32_t>(n);
         q->d_allowed = dalloc<uint64_t>(words);
+        if (use_label && label_defer) q->d_allowed_alt = dalloc<uint64_t>(words);  // (pipelined calls alternate)
         q->d_flags = dalloc<uint64_t>(words);
         if (n) {
             HIP_CHECK(hipMemcpyAsync(q->d_roots, roots, n * 4, hipMemcpyHostToDevice, stream));
@@ -6901,6 +7078,14 @@ struct ketogpu_engine {
         HIP_CHECK(hipSetDevice(device));
         uint64_t words = (q.n + 63) / 64;
         if (q.pending) {  // after this batch's queued call only (later queued calls keep running)
+            // its dense pass: pending (launched now, the event recorded again after it), or
+            // carried by a later launch on its stream (the event recorded again there)
+            for (unsigned k = 0; k < kPipe; k++)
+                if (pend[k].on && pend[k].q == &q) flush_dense(k);
+            if (q.pass == 2) {
+                HIP_CHECK(hipEventRecord(q.done_ev, pstream(q.last_s)));
+                q.pass = 0;
+            }
             HIP_CHECK(hipStreamWaitEvent(copy_stream, q.done_ev, 0));
             if (words && allowed)
                 HIP_CHECK(hipMemcpyAsync(allowed, q.d_allowed, words * 8, hipMemcpyDeviceToHost, copy_stream));
@@ -7006,19 +7191,61 @@ int ketogpu_queries_run_async(ketogpu_engine *e, ketogpu_queries *q, int *queued
     hipStream_t sq = si ? e->pipe_s[si] : e->stream;
     bool elsewhere = false;  // the same batch queued on another stream: after it
     for (unsigned k = 0; k < ketogpu_engine::kPipe; k++) elsewhere |= k != si && e->pipe_q[k] == q;
-    if (elsewhere && q->pending) HIP_CHECK(hipStreamWaitEvent(sq, q->done_ev, 0));
+    // (its dense pass pending there: launched first, the event recorded again after it)
+    for (unsigned k = 0; k < ketogpu_engine::kPipe; k++)
+        if (k != si && e->pend[k].on && e->pend[k].q == q) e->flush_dense(k);
+    if (elsewhere && q->pending) {
+        if (q->pass == 2) {  // (the event not recorded with the call: KETOGPU_LABEL_DONE_EVENT=demand)
+            HIP_CHECK(hipEventRecord(q->done_ev, e->pstream(q->last_s)));
+            q->pass = 0;
+        }
+        HIP_CHECK(hipStreamWaitEvent(sq, q->done_ev, 0));
+    }
+    if (e->use_label && e->label_defer) {
+        // this call writes the batch's other result array: after that array's last queued
+        // writers (a first stage and the launch that carried its pass, both on one stream)
+        if (!q->d_allowed_alt) q->d_allowed_alt = dalloc<uint64_t>(std::max<uint64_t>((q->n + 63) / 64, 1));
+        std::swap(q->d_allowed, q->d_allowed_alt);
+        std::swap(q->wrote, q->wrote_alt);
+        if (q->wrote.epoch == e->pipe_epoch && q->wrote.s != si) {
+            if (!e->order_ev) HIP_CHECK(hipEventCreateWithFlags(&e->order_ev, hipEventDisableTiming));
+            HIP_CHECK(hipEventRecord(e->order_ev, e->pstream(q->wrote.s)));
+            HIP_CHECK(hipStreamWaitEvent(sq, e->order_ev, 0));
+        }
+        q->wrote.s = si;
+        q->wrote.epoch = e->pipe_epoch;
+    }
     if (si) std::swap(e->stream, e->pipe_s[si]);
+    e->cur_pipe = si;
     try {
         e->run(*q);
     } catch (...) {
         if (si) std::swap(e->stream, e->pipe_s[si]);
+        e->cur_pipe = 0;
         e->pipelined_req = false;
+        e->carry_call = false;
         throw;
     }
     if (si) std::swap(e->stream, e->pipe_s[si]);
+    e->cur_pipe = 0;
+    q->pass = 0;
     if (e->queued) {
-        if (!q->done_ev) HIP_CHECK(hipEventCreateWithFlags(&q->done_ev, hipEventDisableTiming));
-        HIP_CHECK(hipEventRecord(q->done_ev, sq));
+        if (e->carry_call) {  // its dense pass is pending on this stream
+            e->pend[si].q = q;
+            q->pass = 1;
+            q->eng = e;
+        }
+        if (!q->done_ev)
+            HIP_CHECK(hipEventCreateWithFlags(
+                &q->done_ev, hipEventDisableTiming | (e->done_mode == 1 ? hipEventDisableSystemFence : 0)));
+        // the call's completion event: the only other packet of a one-launch call on its stream.
+        // `demand`: not recorded here but when it is needed (download, the batch queued on
+        // another stream), on the call's stream as it stands then (pass 2)
+        if (e->done_mode != 2)
+            HIP_CHECK(hipEventRecord(q->done_ev, sq));
+        else if (q->pass == 0)
+            q->pass = 2;
+        q->last_s = si;
         q->pending = true;
         e->pipe_q[si] = q;
         e->pipe_used[si] = true;
@@ -7050,7 +7277,21 @@ int ketogpu_queries_download(ketogpu_engine *e, const ketogpu_queries *q, uint64
     API_END
 }
 
-void ketogpu_queries_free(ketogpu_queries *q) { delete q; }
+void ketogpu_queries_free(ketogpu_queries *q) {
+    if (q && q->pass == 1 && q->eng) {  // its dense pass is pending in the engine: launched before the arrays go
+        ketogpu_engine *e = q->eng;
+        std::lock_guard<std::mutex> lk(e->mu);
+        try {
+            HIP_CHECK(hipSetDevice(e->device));
+            for (unsigned k = 0; k < ketogpu_engine::kPipe; k++)
+                if (e->pend[k].on && e->pend[k].q == q) e->flush_dense(k);
+        } catch (const Error &) {
+            for (unsigned k = 0; k < ketogpu_engine::kPipe; k++)
+                if (e->pend[k].q == q) e->pend[k] = ketogpu_engine::PendingDense{};
+        }
+    }
+    delete q;  // (hipFree waits for the device)
+}
 
 int ketogpu_check_ids(ketogpu_engine *e, const uint32_t *roots, const uint32_t *targets, size_t n,
                       uint64_t *allowed_bits, uint64_t *flagged_bits) {
