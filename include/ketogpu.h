@@ -436,6 +436,12 @@ int ketogpu_queries_download(ketogpu_engine *e, const ketogpu_queries *q, uint64
 int ketogpu_queries_run_async(ketogpu_engine *e, ketogpu_queries *q, int *queued);
 /* waits for every call enqueued on the engine (ketogpu_queries_run_async) */
 int ketogpu_engine_wait(ketogpu_engine *e);
+/* diagnostics: the requests that the most recent separately launched dense pass of a queued
+ * call (plan label) found listed, as read at the engine's last wait or download of such a
+ * call; 0 before the first.  Queued calls answer short P overflows in their first stage
+ * (KETOGPU_LABEL_TAIL), so this is below ketogpu_run_stats.full_requests of a
+ * synchronized call over the same batch. */
+int ketogpu_engine_piped_full_requests(ketogpu_engine *e, uint64_t *out);
 void ketogpu_queries_free(ketogpu_queries *q);
 
 /* statistics of the last run on this engine (for the roofline report) */

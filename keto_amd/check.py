@@ -160,6 +160,13 @@ class Engine:
         """waits for the calls enqueued on this engine (DeviceQueries.run(pipelined=True))"""
         L.check(self.L.ketogpu_engine_wait(self.h))
 
+    def piped_full_requests(self):
+        """the requests the most recent separately launched dense pass of a queued call
+        found listed (read at the last wait or download of such a call; 0 before the first)"""
+        n = C.c_uint64()
+        L.check(self.L.ketogpu_engine_piped_full_requests(self.h, C.byref(n)))
+        return n.value
+
     def set_events(self, every_kernel):
         """host-to-host batches: a timing event between the call's kernels (main_ms = the
         first stage's own time) or only around the call (default)"""

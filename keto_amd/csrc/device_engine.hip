@@ -2662,7 +2662,20 @@ __device__ __forceinline__ bool label_lookup(const uint32_t *row, uint32_t x) {
 // A unit of 16 requests by one wave (four lanes per request), the heads' inline entries
 // only: a request the heads do not settle is listed in F for the dense second pass
 // (label_full_kernel), so no wave waits on one request's second read.
-template <int HS, int HP>
+//
+// TAIL (queued lean calls only, label_carry_kernel; KETOGPU_LABEL_TAIL): the tail phase
+// answers the commonest dense class here, while both heads are in LDS — S whole in its head,
+// P overflowing by at most one more head's worth of entries (CP < np <= 2 CP), the one-edge
+// test settled, and the prefix rule failing only because S has landmarks above P's last
+// inline entry p_last.  Exact by labels.hpp's argument: S's landmarks are all inline; those
+// <= p_last were each compared with P's whole inline prefix by step 1 (and every entry of P
+// <= p_last is inline); those above p_last can only meet P among its entries [CP, np), which
+// the phase reads (one 16-byte aligned run of at most 4 CP bytes in P's overflow region) into
+// the request's own P image row and searches like an inline prefix.  Such a request is
+// settled: it is not listed in F, whether it hit or not.  A wave without one skips the phase
+// (one ballot).  The synchronized and host paths keep TAIL = false: their statistics
+// (full_requests, the entries counter) are pinned to the first stage as it was.
+template <int HS, int HP, bool TAIL = false>
 __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelGraph &L, uint32_t r_lane,
                                            uint32_t t_lane, uint64_t *allowed, const uint64_t unit,
                                            const LabelRest &R, const LabelRest &F, unsigned long long *stats) {
@@ -2744,6 +2757,56 @@ __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelG
             }
         }
     }
+    // 1b. the tail phase (see above): a request of the class reads P's entries [CP, np) over
+    //     its P image row and looks S's landmarks above p_last up in them
+    bool tail = false;
+    if constexpr (TAIL) {
+        const uint64_t hq = __ballot(hit);
+        bool tq = labelled && !((hq >> (lane & ~3u)) & 0xF) && np > CP && np <= 2 * CP && es > 0;
+        uint32_t p_last = 0;
+        if (tq) {  // (the quad's four lanes alike)
+            const uint32_t s_end = Se[CS - 1];
+            p_last = Pe[CP - 1];
+            const bool s_whole = ns <= CS || s_end >= L.ni, raw_done = r < L.ni || ns <= CS || r <= s_end;
+            tq = s_whole && raw_done && Se[es - 1] > p_last;
+        }
+        if (__ballot(tq)) {  // (wave-uniform: a wave without such a request runs the code as it was)
+            // the candidates: positions k0 .. es - 1 of S's image, k0 = its entries <= p_last
+            // (p_last < Ni: neither a raw entry nor a pad counts), counted as es is
+            uint32_t k0 = 0;
+#pragma unroll
+            for (int k = 0; k < SW; k++) k0 += (k >= (int)kHeadFixed || s_body) && sw[k] <= p_last;
+            k0 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)k0, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
+            k0 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)k0, 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
+            // the tail: CP / 4 16-byte units from word CP of the list at P + 16 op, unit i by
+            // lane i mod 4 of the quad, all in flight before any is used; only units that
+            // hold an entry below np are read (CP + 4 i < np <= 16 ceil(np / 16): inside the
+            // region), and the words at or past np are masked — a list rewritten in place on
+            // a writable snapshot (label_update) may leave anything behind its end
+            constexpr int NT = (int)CP / 4, NL = (NT + 3) / 4;  // units, units per lane
+            const uint4 *Tg = reinterpret_cast<const uint4 *>(L.P + (uint64_t)label_word<PW, 1>(pw) * 16) + CP / 4;
+            uint4 tv[NL];
+#pragma unroll
+            for (int j = 0; j < NL; j++) {
+                const uint32_t i = sub + 4 * j;
+                tv[j] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+                if (tq && i < (uint32_t)NT && CP + 4 * i < np) tv[j] = Tg[i];
+            }
+            wave_sync();  // (every lane has read p_last and ended its walk of the P image)
+#pragma unroll
+            for (int j = 0; j < NL; j++) {
+                const uint32_t i = sub + 4 * j, w = CP + 4 * i;
+                if (tq && i < (uint32_t)NT)
+                    reinterpret_cast<uint4 *>(Pl)[1 + i] =
+                        make_uint4(w < np ? tv[j].x : 0xFFFFFFFFu, w + 1 < np ? tv[j].y : 0xFFFFFFFFu,
+                                   w + 2 < np ? tv[j].z : 0xFFFFFFFFu, w + 3 < np ? tv[j].w : 0xFFFFFFFFu);
+            }
+            wave_sync();
+            if (tq)
+                for (uint32_t k = k0 + sub; k < es && !hit; k += 4) hit = label_lookup<CP, HP>(Pl, Se[k]);
+            tail = tq;
+        }
+    }
     // 2. a request neither hit nor settled by its heads (labels.hpp): listed for
     //    label_full_kernel, with both counts and overflow starts (the dense pass then needs no
     //    head again).  Settled: no landmark can be missing from the prefixes — S's landmarks
@@ -2754,7 +2817,7 @@ __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelG
         const uint64_t hb = __ballot(hit);
         const uint32_t os = label_word<SW, 1>(sw), op = label_word<PW, 1>(pw);
         bool full = false;
-        if (sub == 0 && labelled && !((hb >> lane) & 0xF)) {
+        if (sub == 0 && labelled && !tail && !((hb >> lane) & 0xF)) {  // (tail: settled by 1b, its P row rewritten)
             const uint32_t s_end = Se[CS - 1];  // (ns > CS: the last inline entry)
             const bool s_whole = ns <= CS || s_end >= L.ni, p_whole = np <= CP;
             const uint32_t s_last = es ? Se[es - 1] : 0u, p_last = ep ? Pe[ep - 1] : 0u;
@@ -3051,8 +3114,10 @@ __global__ __launch_bounds__(64) void label_full_kernel(LabelGraph L, uint64_t *
 // chains of dependent reads start at once and run under the whole first stage.  They reuse
 // the unit's head images as their stage (16 rows of HS + HP + 8 words, a longer list is
 // searched in global memory) with 4 walked entries and 2 staging loads per lane in flight, so
-// the kernel holds as many workgroups per CU as label_kernel does.
-template <int HS, int HP>
+// the kernel holds as many workgroups per CU as label_kernel does.  TAIL: the first stage
+// settles short P overflows itself (label_unit's tail phase), so the next launch's dense
+// role finds about a sixth of the records (config #2).
+template <int HS, int HP, bool TAIL>
 __global__ __launch_bounds__(64) void label_carry_kernel(LabelGraph L, const uint32_t *roots, const uint32_t *targets,
                                                          uint64_t n, uint64_t *allowed, LabelRest R, LabelRest F,
                                                          LabelRest Fd, uint64_t *allowed_d, uint32_t D) {
@@ -3071,7 +3136,7 @@ __global__ __launch_bounds__(64) void label_carry_kernel(LabelGraph L, const uin
     const uint64_t unit = blockIdx.x - D;
     uint32_t r, t;
     bidi_load_rt<16>(unit, units, roots, targets, n, r, t);
-    label_unit<HS, HP>(sh, L, r, t, allowed, unit, R, F, nullptr);
+    label_unit<HS, HP, TAIL>(sh, L, r, t, allowed, unit, R, F, nullptr);
     // the last result word's 16-bit parts past the last unit (no unit writes them)
     if (unit + 1 == units && threadIdx.x == 0)
         for (uint64_t u = units; u < (units + 3) / 4 * 4; u++) reinterpret_cast<uint16_t *>(allowed)[u] = 0;
@@ -4782,19 +4847,40 @@ struct ketogpu_engine {
         if (k == cur_pipe) return stream;
         return k ? pipe_s[k] : pipe_s[cur_pipe];
     }
-    unsigned dense_grid() const { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(full_prev / 16 + 64, 64), 16384); }
-    void flush_dense(unsigned k) {
+    // KETOGPU_LABEL_TAIL (default on; 0: queued calls launch the carrying kernel without the
+    // tail phase, label_unit): short P overflows are answered inside the first stage
+    bool label_tail = [] {
+        const char *e = getenv("KETOGPU_LABEL_TAIL");
+        return !e || atoi(e) != 0;
+    }();
+    // the requests the most recent flushed pass of a queued call found listed: queued calls
+    // list fewer than synchronized ones (the tail phase), so their passes are sized by their
+    // own count.  label_full_kernel writes its list's total into the host-mapped mirror; it
+    // is read where the host waits for that launch anyway (drain_pipe, download)
+    uint64_t piped_full = 0;
+    bool piped_full_known = false, flush_unread = false;
+    void take_piped_full() {
+        piped_full = ((const unsigned int *)(h_ctr + 24))[7];
+        piped_full_known = true;
+    }
+    static unsigned grid_for(uint64_t full) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(full / 16 + 64, 64), 16384); }
+    unsigned dense_grid() const { return grid_for(full_prev); }
+    // a queued call's pass (carried or flushed); the persistent loop is correct for any grid
+    unsigned piped_grid() const { return grid_for(piped_full_known ? piped_full : full_prev); }
+    bool flush_dense(unsigned k) {
         PendingDense p = pend[k];
-        if (!p.on) return;
+        if (!p.on) return false;
         pend[k] = PendingDense{};
         label_dispatch([&](auto hs, auto hp) {
-            KLAUNCH((label_full_kernel<decltype(hs)::value, decltype(hp)::value>), dim3(dense_grid()), dim3(64), 0,
+            KLAUNCH((label_full_kernel<decltype(hs)::value, decltype(hp)::value>), dim3(piped_grid()), dim3(64), 0,
                     pstream(k), lgraph, p.allowed, p.R, p.F, &spill_count[0], &spill_count[7], nullptr, d_hctr + 16);
         });
+        flush_unread = true;
         if (p.q) {  // the batch's results are complete at its event again
             if (p.q->done_ev) HIP_CHECK(hipEventRecord(p.q->done_ev, pstream(k)));
             p.q->pass = 0;
         }
+        return true;
     }
     void flush_dense_all() {
         for (unsigned k = 0; k < kPipe; k++) flush_dense(k);
@@ -4807,6 +4893,8 @@ struct ketogpu_engine {
             if (pipe_used[k]) HIP_CHECK(hipStreamSynchronize(pstream(k)));
             pipe_used[k] = false;
         }
+        if (flush_unread) take_piped_full();  // (every flushed pass is complete)
+        flush_unread = false;
         pipe_epoch++;
     }
     bool pipe_busy() const {
@@ -6402,11 +6490,16 @@ struct ketogpu_engine {
                     // stream (the previous queued call's here)
                     PendingDense p = pend[cur_pipe];
                     pend[cur_pipe] = PendingDense{};
-                    const unsigned D = p.on ? dense_grid() : 0u;
+                    const unsigned D = p.on ? piped_grid() : 0u;
                     label_dispatch([&](auto hs, auto hp) {
-                        KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value>),
-                                dim3(D + (unsigned)bunits), dim3(64), lds_pad, stream, lgraph, q.roots, q.targets, q.n,
-                                q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D);
+                        if (label_tail)
+                            KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value, true>),
+                                    dim3(D + (unsigned)bunits), dim3(64), lds_pad, stream, lgraph, q.roots, q.targets,
+                                    q.n, q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D);
+                        else
+                            KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value, false>),
+                                    dim3(D + (unsigned)bunits), dim3(64), lds_pad, stream, lgraph, q.roots, q.targets,
+                                    q.n, q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D);
                     });
                     if (p.q) p.q->pass = 2;
                 } else if (!src) {
@@ -7080,8 +7173,9 @@ struct ketogpu_engine {
         if (q.pending) {  // after this batch's queued call only (later queued calls keep running)
             // its dense pass: pending (launched now, the event recorded again after it), or
             // carried by a later launch on its stream (the event recorded again there)
+            bool flushed = false;
             for (unsigned k = 0; k < kPipe; k++)
-                if (pend[k].on && pend[k].q == &q) flush_dense(k);
+                if (pend[k].on && pend[k].q == &q) flushed |= flush_dense(k);
             if (q.pass == 2) {
                 HIP_CHECK(hipEventRecord(q.done_ev, pstream(q.last_s)));
                 q.pass = 0;
@@ -7092,6 +7186,7 @@ struct ketogpu_engine {
             if (words && flagged)
                 HIP_CHECK(hipMemcpyAsync(flagged, q.d_flags, words * 8, hipMemcpyDeviceToHost, copy_stream));
             HIP_CHECK(hipStreamSynchronize(copy_stream));
+            if (flushed) take_piped_full();  // (the pass flushed above is complete: the event follows it)
             q.pending = false;
             return;
         }
@@ -7265,6 +7360,14 @@ int ketogpu_engine_wait(ketogpu_engine *e) {
     HIP_CHECK(hipSetDevice(e->device));
     e->drain_pipe();
     HIP_CHECK(hipStreamSynchronize(e->stream));
+    API_END
+}
+
+int ketogpu_engine_piped_full_requests(ketogpu_engine *e, uint64_t *out) {
+    API_BEGIN
+    if (!e || !out) throw Error(KETOGPU_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    *out = e->piped_full_known ? e->piped_full : 0;
     API_END
 }
 

@@ -45,6 +45,16 @@
 // last inline entry (a common landmark would then lie in both prefixes) — and the raw test
 // is settled (r interior, S whole in its head, or r <= its last inline entry).  Otherwise
 // the dense pass reads the overflow lists.
+//
+// The tail phase (queued calls' first stage, KETOGPU_LABEL_TAIL) settles one more class from
+// the heads plus one short read: S's landmarks whole in its head, the raw test settled, P
+// overflowing with CP < np <= 2 CP (CP = P's inline entries) and S's last inline landmark
+// above P's last inline entry p_last.  S's landmarks are all inline.  Those <= p_last were
+// each compared with P's whole inline prefix by the first stage, and every entry of P that
+// is <= p_last lies in that prefix (the list ascends), so none of them is shared.  Those
+// above p_last can only meet P among its entries [CP, np): the phase reads exactly these
+// from P's overflow region and searches them.  With the one-edge test settled the request
+// is decided, hit or not, and never reaches the dense pass.
 #pragma once
 
 #include <cstdint>
