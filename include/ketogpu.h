@@ -15,6 +15,8 @@
  *   ketogpu_queries_*      inputs resident in HBM
  *   ketogpu_expand         (*expand.Engine).BuildTree internal/expand/engine.go:30-98
  *   ketogpu_tree_*         expand.Tree / its JSON codec internal/expand/tree.go:26-30,85-91,156-162
+ *   ketogpu_lookup_*       the reverse question (no reference counterpart): every object a
+ *                          subject reaches, by the same SubjectIsAllowed semantics
  *
  * Conventions: plain C types only; all input memory is copied (cgo pointer rules);
  * opaque handles are owned by the library; result buffers are caller-allocated.
@@ -932,6 +934,88 @@ int ketogpu_tree_nodes(const ketogpu_tree *t, const ketogpu_tree_node **nodes, s
 /* MarshalJSON of the tree (tree.go:156-162); free with ketogpu_free */
 int ketogpu_tree_json(const ketogpu_tree *t, char **json);
 void ketogpu_tree_free(ketogpu_tree *t);
+
+/* ---------------------------------------------------------- reverse lookup */
+/* "Which objects can this subject reach?" (OpenFGA ListObjects, SpiceDB LookupResources; the
+ * reference has only the forward question, internal/check/engine.go:93-95).  For a target node
+ * t and an object type T, lookup(t, T) is the set of expandable nodes r (r < num_expandable) of
+ * type T for which SubjectIsAllowed(r, t) is true, without duplicates: the backward closure
+ * B(t) over the reverse rows (DESIGN.md "Reverse lookup"), so its cost follows the answer and
+ * not the namespace.  t itself is listed only when a cycle leads back to it (R2).
+ *
+ * The TYPE of an expandable node is its interned pair (namespace id, relation).  Wildcard
+ * subject-set nodes (R5: an empty field) are expandable nodes like any other and are listed
+ * under KETOGPU_TYPE_ANY, but have types of their own that no (namespace, relation) pair
+ * resolves to, so a concrete type leaves them out.  Dynamic wildcard roots (queries without a
+ * snapshot node) are not nodes and are never listed.  The placeholder nodes of a writable
+ * snapshot are never listed.  Snapshots with shared Subject.String() keys (R4) are refused with
+ * KETOGPU_EINVAL, as in the partitioned mode: the formula does not hold there.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+#define KETOGPU_TYPE_ANY 0xFFFFFFFFu  /* no type filter                                      */
+#define KETOGPU_TYPE_NONE 0xFFFFFFFEu /* matches nothing: unknown namespace or unused pair
+                                         (R6: check maps NotFound to false)                 */
+/* (namespace name, relation) -> type id, or KETOGPU_TYPE_NONE (the call still returns
+ * KETOGPU_OK).  Type ids are stable for the life of the snapshot. */
+int ketogpu_snapshot_type(const ketogpu_snapshot *s, const char *ns_name, const char *relation, uint32_t *type);
+/* What a node id stands for.  The strings are pointer + length (not 0-terminated) into memory
+ * owned by the snapshot, valid while it lives.  KETOGPU_EINVAL for ids >= num_nodes and for the
+ * placeholder nodes of a writable snapshot. */
+typedef struct {
+    int32_t kind;         /* KETOGPU_SUBJECT_ID / KETOGPU_SUBJECT_SET                      */
+    int32_t namespace_id; /* subject set: its namespace id; subject id: 0                  */
+    uint32_t type;        /* expandable node: its type; any other node: KETOGPU_TYPE_NONE  */
+    uint32_t expandable;  /* 1: id < num_expandable (the node can be listed)               */
+    const char *ns;       /* subject set: configured name of namespace_id ("" if none)     */
+    size_t ns_len;
+    const char *id;       /* subject set: the object; subject id: the id                   */
+    size_t id_len;
+    const char *rel;      /* subject set: the relation                                     */
+    size_t rel_len;
+} ketogpu_node_info;
+int ketogpu_snapshot_node(const ketogpu_snapshot *s, uint32_t id, ketogpu_node_info *out);
+/* lookup(target, type) on the host, over the snapshot's reverse rows: *ids ascending, *n its
+ * length; free *ids with ketogpu_free.  target KETOGPU_NODE_NONE: the empty list; any other
+ * id >= num_nodes: KETOGPU_EINVAL.  Needs no GPU; the yardstick of ketogpu_lookup_ids. */
+int ketogpu_snapshot_lookup(const ketogpu_snapshot *s, uint32_t target, uint32_t type, uint32_t **ids, uint64_t *n);
+
+/* The device side: a handle of its own over the snapshot's reverse rows and type array in HBM.
+ * Every call compares ketogpu_snapshot_version with the version it uploaded and uploads the
+ * rows again when a ketogpu_snapshot_write moved it (O(reverse rows), not O(delta)). */
+typedef struct ketogpu_lookup ketogpu_lookup;
+typedef struct {
+    int32_t device;              /* HIP device ordinal                                      */
+    uint64_t state_budget_bytes; /* HBM for tier 2's per-slot state; 0 = at most 1/8 of the
+                                    free HBM                                                */
+} ketogpu_lookup_opts;
+typedef struct {
+    uint64_t requests;       /* since creation: targets passed in                          */
+    uint64_t tier1_requests; /* answered by the one-wave LDS kernel                        */
+    uint64_t tier2_requests; /* answered by the workgroup-per-request kernel               */
+    uint64_t tier2_rounds;   /* tier-2 launches (each serves up to `slots` requests)       */
+    uint64_t ids_produced;   /* sum of the exact list sizes                                */
+    uint64_t truncated_lists;
+    uint64_t uploads;        /* row uploads (1 at creation, +1 per version change seen)    */
+    uint32_t set_capacity;   /* tier 1: nodes B(t) may hold before the request moves on    */
+    uint32_t slots;          /* tier 2: requests per round (0 before the first round)      */
+    double last_call_ms;     /* host wall time of the last ketogpu_lookup_ids              */
+} ketogpu_lookup_stats;
+/* KETOGPU_LOOKUP_TIER=2 (environment, read here) sends every request to tier 2;
+ * KETOGPU_LOOKUP_SLOTS=k caps tier 2's slots. */
+int ketogpu_lookup_new(const ketogpu_snapshot *s, const ketogpu_lookup_opts *opts, ketogpu_lookup **out);
+void ketogpu_lookup_free(ketogpu_lookup *l);
+int ketogpu_lookup_stats_get(const ketogpu_lookup *l, ketogpu_lookup_stats *out);
+/* lookup(targets[i], type) for n targets in one call.  count[i] is always the exact size of
+ * list i; begin[i] is the offset in `out` of list i, written completely, or a marker:
+ * TRUNCATED (the list did not fit in `capacity` ids; nothing of it was written) or INVALID
+ * (targets[i] >= num_nodes and not KETOGPU_NODE_NONE; count 0).  KETOGPU_NODE_NONE gives an
+ * empty list.  *needed = the sum of all counts; needed <= capacity guarantees that nothing was
+ * truncated (every request reserves exactly count[i] ids).  Lists lie in `out` in any order,
+ * the ids inside a list in any order, without duplicates.  capacity 0 with out NULL is the
+ * count-only call.  Returns KETOGPU_OK also when lists were truncated. */
+#define KETOGPU_LOOKUP_TRUNCATED UINT64_MAX
+#define KETOGPU_LOOKUP_INVALID (UINT64_MAX - 1)
+int ketogpu_lookup_ids(ketogpu_lookup *l, const uint32_t *targets, size_t n, uint32_t type, uint32_t *out,
+                       uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
 
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);

@@ -21,6 +21,8 @@ BUILD_WRITABLE = 4  # rows with free slots: ketogpu_snapshot_write patches in pl
 WRITE_REASONS = {0: "applied", 1: "not_writable", 2: "wildcard", 3: "poison", 4: "class", 5: "ambiguous",
                  6: "full", 7: "reserve", 8: "fanout"}
 NODE_UNION, NODE_LEAF = 0, 1
+TYPE_ANY, TYPE_NONE = 0xFFFFFFFF, 0xFFFFFFFE  # reverse lookup: no type filter / matches nothing
+LOOKUP_TRUNCATED, LOOKUP_INVALID = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE
 
 
 class KetoError(Exception):
@@ -300,6 +302,26 @@ class TierSteps(C.Structure):
                 ("reply_emit", TIER_REPLY_EMIT_FN), ("evaluate", TIER_EVALUATE_FN)]
 
 
+# include/ketogpu.h reverse lookup
+class NodeInfo(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("namespace_id", C.c_int32), ("type", C.c_uint32), ("expandable", C.c_uint32),
+                ("ns", C.c_void_p), ("ns_len", C.c_size_t), ("id", C.c_void_p), ("id_len", C.c_size_t),
+                ("rel", C.c_void_p), ("rel_len", C.c_size_t)]
+
+
+class LookupOpts(C.Structure):
+    _fields_ = [("device", C.c_int32), ("state_budget_bytes", C.c_uint64)]
+
+
+class LookupStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "requests", "tier1_requests", "tier2_requests", "tier2_rounds", "ids_produced", "truncated_lists",
+        "uploads")] + [("set_capacity", C.c_uint32), ("slots", C.c_uint32), ("last_call_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol declared in include/ketogpu.h, with its ctypes signature
 vp, i32, u32, sz = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t
 SIGNATURES = {
@@ -420,6 +442,13 @@ SIGNATURES = {
     "ketogpu_tier_check_ids": (C.c_int, [vp, vp, vp, sz, vp]),
     "ketogpu_tier_stats_get": (C.c_int, [vp, C.POINTER(TierStats)]),
     "ketogpu_tier_free": (None, [vp]),
+    "ketogpu_snapshot_type": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.POINTER(u32)]),
+    "ketogpu_snapshot_node": (C.c_int, [vp, u32, C.POINTER(NodeInfo)]),
+    "ketogpu_snapshot_lookup": (C.c_int, [vp, u32, u32, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_new": (C.c_int, [vp, C.POINTER(LookupOpts), C.POINTER(vp)]),
+    "ketogpu_lookup_free": (None, [vp]),
+    "ketogpu_lookup_stats_get": (C.c_int, [vp, C.POINTER(LookupStats)]),
+    "ketogpu_lookup_ids": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

@@ -138,6 +138,7 @@ struct RowRef {
 };
 
 struct ReachLabels;  // labels.hpp
+struct TypeIndex;    // lookup.hpp
 
 struct Snapshot {
     // ---- configuration
@@ -231,6 +232,9 @@ struct Snapshot {
     mutable std::shared_ptr<const ReachLabels> reach_cache;
     mutable std::shared_future<std::shared_ptr<const ReachLabels>> reach_building;
     mutable uint64_t reach_building_version = ~0ull;
+    // reverse lookup's per-node object types (lookup.hpp type_index_of), derived per version
+    mutable std::shared_ptr<const TypeIndex> type_cache;
+    mutable uint64_t type_cache_version = ~0ull;
     // An engine's way back to its snapshot at teardown: the snapshot's destructor clears it,
     // so an engine freed after its snapshot (a garbage collector's order) skips the
     // deregistration instead of touching freed memory.

@@ -1,0 +1,469 @@
+// lookup.hip — reverse lookup on the device (include/ketogpu.h ketogpu_lookup_*).
+//
+// lookup(t, T) lists B(t), the expandable nodes that reach t in >= 1 edge, restricted to the
+// object type T: the least set that holds rev(t) and rev(x) for every x in it (DESIGN.md
+// "Reverse lookup").  Only interior entries (ids < Ni) have reverse rows, so only they are put
+// on a worklist.  Two kernels:
+//
+//   tier 1  one wave per request.  B(t) lives in an LDS open-addressing set (insert by LDS
+//           compare-and-swap) that is visited set and result at once; the interior members
+//           also go on an LDS worklist (each enters once, so it needs no more room than the
+//           set).  Rows are read 64 entries per step.  A request whose set passes kSetCap is
+//           appended to the overflow list and leaves no output.
+//   tier 2  one workgroup per overflow request, `slots` requests per launch.  Each slot has a
+//           bitmap over the expandable nodes and a worklist of Ni entries in global memory; a
+//           level loop with __syncthreads() runs the closure to its end whatever its size.
+//
+// Both end the same way: count the members of type T, reserve exactly that many ids of `out`
+// with one device-scope atomicAdd on a cursor, and write the list with plain vector stores if
+// it fits below `capacity` (else begin = TRUNCATED; the count is exact either way).  The cursor
+// ends at the sum of the counts, so a capacity of at least that sum truncates nothing.
+//
+// Every index is validated before it is used: targets against num_nodes before rev_off is
+// touched, row entries against num_expandable before the type array or a bitmap is.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdlib>
+
+#include "lookup.hpp"
+
+using namespace ketogpu;
+
+namespace {
+
+constexpr uint32_t kSetCap = 1024;         // tier 1: nodes a set may hold (ketogpu_lookup_stats.set_capacity)
+constexpr uint32_t kSlotsLds = 2 * kSetCap;  // hash slots: a load of at most (kSetCap + 64) / kSlotsLds
+constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+constexpr unsigned kT2Block = 256;
+
+struct LGraph {
+    const uint64_t *rev_off;   // N + 1 (a writable snapshot: n_cap + 1)
+    const uint32_t *rev_col;
+    const uint32_t *node_type; // Nx
+    uint32_t N, Nx, Ni;
+};
+
+struct LOut {
+    uint32_t *out;
+    unsigned long long capacity;
+    unsigned long long *begin, *count;
+    unsigned long long *cursor;  // ids reserved so far: ends at `needed`
+    unsigned long long *truncated;
+};
+
+__device__ inline bool type_ok(const LGraph &g, uint32_t u, uint32_t want) {
+    if (u >= g.Nx) return false;
+    const uint32_t ty = g.node_type[u];
+    return want == KETOGPU_TYPE_ANY ? ty != KETOGPU_TYPE_NONE : (want != KETOGPU_TYPE_NONE && ty == want);
+}
+
+__device__ inline uint32_t slot_of(uint32_t u) { return (u * 0x9E3779B1u) >> 21; }  // 11 bits
+static_assert(kSlotsLds == 1u << 11, "slot_of yields 11 bits");
+
+// ---------------------------------------------------------------------- tier 1
+__global__ __launch_bounds__(64) void lookup_tier1_kernel(LGraph g, const uint32_t *targets, uint32_t n, uint32_t type,
+                                                          int force_tier2, LOut o, uint32_t *ovf_list,
+                                                          unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = targets[i];
+    if (t >= g.N) {  // NONE: the empty list; any other id outside the snapshot: INVALID
+        if (lane == 0) {
+            o.begin[i] = t == KETOGPU_NODE_NONE ? 0ull : KETOGPU_LOOKUP_INVALID;
+            o.count[i] = 0;
+        }
+        return;
+    }
+    if (force_tier2) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    for (uint32_t s = lane; s < kSlotsLds; s += 64) set[s] = kEmpty;
+    __syncthreads();
+    uint32_t size = 0, head = 0, tail = 0;  // wave-uniform
+    bool over = false;
+    uint32_t v = t;
+    for (;;) {
+        const uint64_t b = g.rev_off[v], e = g.rev_off[v + 1];
+        for (uint64_t base = b; base < e && !over; base += 64) {
+            const uint64_t j = base + lane;
+            const uint32_t u = j < e ? g.rev_col[j] : kEmpty;
+            bool fresh = false;
+            if (u < g.Nx) {  // (also drops kEmpty) — the set never holds more than kSetCap + 64 of
+                             // its 2 x kSetCap slots, so the probe ends at a free slot
+                uint32_t s = slot_of(u);
+                for (;;) {
+                    const uint32_t old = atomicCAS(&set[s], kEmpty, u);
+                    if (old == kEmpty) {
+                        fresh = true;
+                        break;
+                    }
+                    if (old == u) break;
+                    s = (s + 1) & (kSlotsLds - 1);
+                }
+            }
+            const unsigned long long mf = __ballot(fresh), mi = __ballot(fresh && u < g.Ni);
+            if (fresh && u < g.Ni) work[tail + __popcll(mi & ((1ull << lane) - 1))] = u;
+            tail += __popcll(mi);
+            size += __popcll(mf);
+            over = size > kSetCap;
+        }
+        __syncthreads();  // the worklist entries of this row are visible to every lane
+        if (over || head == tail) break;
+        v = work[head++];
+    }
+    if (over) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    uint32_t cnt = 0;
+    for (uint32_t s = lane; s < kSlotsLds; s += 64) cnt += __popcll(__ballot(type_ok(g, set[s], type)));
+    unsigned long long base = 0;
+    if (lane == 0) {
+        base = atomicAdd(o.cursor, (unsigned long long)cnt);
+        const bool fits = base + cnt <= o.capacity;
+        o.count[i] = cnt;
+        o.begin[i] = fits ? base : KETOGPU_LOOKUP_TRUNCATED;
+        if (!fits) atomicAdd(o.truncated, 1ull);
+    }
+    base = __shfl(base, 0);
+    if (base + cnt > o.capacity || !cnt) return;
+    uint32_t w = 0;
+    for (uint32_t s = lane; s < kSlotsLds; s += 64) {
+        const uint32_t u = set[s];
+        const bool m = type_ok(g, u, type);
+        const unsigned long long mm = __ballot(m);
+        if (m) o.out[base + w + __popcll(mm & ((1ull << lane) - 1))] = u;
+        w += __popcll(mm);
+    }
+}
+
+// ---------------------------------------------------------------------- tier 2
+// Block s of round r serves overflow request ovf_list[first + s] with slot s's state.  The
+// bitmap is all zero on entry and is cleared again on the way out.
+__global__ __launch_bounds__(kT2Block) void lookup_tier2_kernel(LGraph g, const uint32_t *targets, uint32_t type,
+                                                                LOut o, const uint32_t *ovf_list, uint32_t first,
+                                                                uint32_t *bitmaps, uint64_t bm_words, uint32_t *worklists) {
+    __shared__ unsigned int s_tail, s_cnt, s_pos;
+    __shared__ unsigned long long s_base;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const uint32_t t = targets[i];
+    uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
+    uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = kT2Block / 64;
+    if (tid == 0) s_tail = 0, s_cnt = 0, s_pos = 0;
+    __syncthreads();
+    if (t >= g.N) return;  // (tier 1 lists valid targets only)
+    auto visit = [&](uint32_t u) {
+        if (u >= g.Nx) return;
+        const uint32_t bit = 1u << (u & 31);
+        if (atomicOr(&bm[u >> 5], bit) & bit) return;
+        if (u < g.Ni) wl[atomicAdd(&s_tail, 1u)] = u;  // each interior node enters once: <= Ni entries
+    };
+    {  // the target's own row, by the whole workgroup
+        const uint64_t b = g.rev_off[t], e = g.rev_off[t + 1];
+        for (uint64_t j = b + tid; j < e; j += kT2Block) visit(g.rev_col[j]);
+    }
+    __syncthreads();
+    uint32_t lb = 0, le = s_tail;
+    while (lb < le) {  // one level: a wave per row
+        __syncthreads();  // everyone has read s_tail before it moves
+        for (uint32_t k = lb + wave; k < le; k += nwaves) {
+            const uint32_t v = wl[k];
+            const uint64_t b = g.rev_off[v], e = g.rev_off[v + 1];
+            for (uint64_t j = b + lane; j < e; j += 64) visit(g.rev_col[j]);
+        }
+        __syncthreads();
+        lb = le;
+        le = s_tail;
+    }
+    // count the members of the type
+    uint32_t c = 0;
+    for (uint64_t w = tid; w < bm_words; w += kT2Block) {
+        uint32_t bits = bm[w];
+        while (bits) {
+            const uint32_t u = (uint32_t)(w << 5) + (uint32_t)__ffs(bits) - 1;
+            bits &= bits - 1;
+            c += type_ok(g, u, type);
+        }
+    }
+    if (c) atomicAdd(&s_cnt, c);
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned long long cnt = s_cnt, base = atomicAdd(o.cursor, cnt);
+        const bool fits = base + cnt <= o.capacity;
+        o.count[i] = cnt;
+        o.begin[i] = fits ? base : KETOGPU_LOOKUP_TRUNCATED;
+        if (!fits) atomicAdd(o.truncated, 1ull);
+        s_base = fits ? base : KETOGPU_LOOKUP_TRUNCATED;
+    }
+    __syncthreads();
+    const unsigned long long base = s_base;
+    for (uint64_t w = tid; w < bm_words; w += kT2Block) {
+        uint32_t bits = bm[w];
+        if (!bits) continue;
+        bm[w] = 0;
+        if (base == KETOGPU_LOOKUP_TRUNCATED) continue;
+        uint32_t ids[32], k = 0;
+        while (bits) {
+            const uint32_t u = (uint32_t)(w << 5) + (uint32_t)__ffs(bits) - 1;
+            bits &= bits - 1;
+            if (type_ok(g, u, type)) ids[k++] = u;
+        }
+        if (!k) continue;
+        const uint32_t p = atomicAdd(&s_pos, k);
+        for (uint32_t x = 0; x < k; x++) o.out[base + p + x] = ids[x];
+    }
+}
+
+#define HIP_CHECK(x)                                                                                   \
+    do {                                                                                               \
+        hipError_t _e = (x);                                                                           \
+        if (_e != hipSuccess)                                                                          \
+            throw Error(KETOGPU_EDEVICE, std::string(#x) + ": " + hipGetErrorString(_e));              \
+    } while (0)
+
+// every launch is checked: a failed launch must fail its call, not a later one
+#define KLAUNCH(...)                                 \
+    do {                                             \
+        hipLaunchKernelGGL(__VA_ARGS__);             \
+        HIP_CHECK(hipGetLastError());                \
+    } while (0)
+
+// a device array that only grows
+template <class T>
+struct DBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    void need(size_t n) {
+        if (n <= cap && p) return;
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+        void *q = nullptr;
+        n = std::max<size_t>(n, 1);
+        hipError_t e = hipMalloc(&q, n * sizeof(T));
+        if (e != hipSuccess) throw Error(KETOGPU_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+        p = (T *)q, cap = n;
+    }
+    void drop() {
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
+};
+
+}  // namespace
+
+struct ketogpu_lookup {
+    std::shared_ptr<Snapshot::ReaderLink> link;  // cleared when the snapshot is freed first
+    int device = 0;
+    uint64_t budget = 0;
+    bool force_tier2 = false;
+    uint32_t slot_cap = 0;  // KETOGPU_LOOKUP_SLOTS (0: no cap)
+    hipStream_t stream = nullptr;
+    std::mutex mu;          // one call at a time per handle
+    uint64_t version = ~0ull;
+    LGraph g{};
+    DBuf<uint64_t> d_off;
+    DBuf<uint32_t> d_col, d_type, d_targets, d_ovf, d_out, d_bm, d_wl;
+    DBuf<unsigned long long> d_begin, d_count, d_ctr;  // d_ctr: cursor, truncated, overflow count
+    uint32_t slots = 0, slot_max = 0;  // tier 2: allocated slots; what budget and knob allow (0: not yet known)
+    uint64_t bm_words = 0;
+    ketogpu_lookup_stats st{};
+
+    // the rows and types of the snapshot's current version (caller holds its shared lock)
+    void upload(const Snapshot &s) {
+        if (s.has_ambiguous)
+            throw Error(KETOGPU_EINVAL, "reverse lookup: the snapshot has shared Subject.String() keys (R4)");
+        auto types = type_index_of(s);
+        d_off.need(s.rev_off.size());
+        d_col.need(s.rev_col.size());
+        d_type.need(types->node_type.size());
+        HIP_CHECK(hipMemcpyAsync(d_off.p, s.rev_off.data(), s.rev_off.size() * 8, hipMemcpyHostToDevice, stream));
+        if (!s.rev_col.empty())
+            HIP_CHECK(hipMemcpyAsync(d_col.p, s.rev_col.data(), s.rev_col.size() * 4, hipMemcpyHostToDevice, stream));
+        if (!types->node_type.empty())
+            HIP_CHECK(hipMemcpyAsync(d_type.p, types->node_type.data(), types->node_type.size() * 4,
+                                     hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        if (s.Nx != g.Nx || s.Ni != g.Ni) slots = 0, slot_max = 0, d_bm.drop(), d_wl.drop();  // tier 2's state follows the sizes
+        g = LGraph{d_off.p, d_col.p, d_type.p, s.N, s.Nx, s.Ni};
+        version = s.version;
+        st.uploads++;
+    }
+
+    // tier 2's state: as many slots as the batch at hand can use, within what the budget allows
+    // (at least one); a later batch with more overflows allocates again
+    void need_slots(uint32_t wanted) {
+        if (!slot_max) {
+            bm_words = ((uint64_t)g.Nx + 31) / 32;
+            const uint64_t per = (bm_words + std::max<uint32_t>(g.Ni, 1)) * 4;
+            uint64_t b = budget;
+            if (!b) {
+                size_t fr = 0, tot = 0;
+                HIP_CHECK(hipMemGetInfo(&fr, &tot));
+                b = fr / 8;
+            }
+            slot_max = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(b / per, 1), 1024);
+            if (slot_cap) slot_max = std::min(slot_max, slot_cap);
+        }
+        uint64_t k = 1;
+        while (k < wanted) k *= 2;
+        k = std::min<uint64_t>(k, slot_max);
+        if (k <= slots) return;
+        slots = 0;  // (an allocation that fails below leaves no half-prepared state behind)
+        d_bm.need(k * std::max<uint64_t>(bm_words, 1));
+        d_wl.need(k * std::max<uint32_t>(g.Ni, 1));
+        HIP_CHECK(hipMemsetAsync(d_bm.p, 0, k * std::max<uint64_t>(bm_words, 1) * 4, stream));
+        slots = (uint32_t)k;
+        st.slots = slots;
+    }
+
+    void run(const uint32_t *targets, size_t n, uint32_t type, uint32_t *out, uint64_t capacity, uint64_t *begin,
+             uint64_t *count, uint64_t *needed) {
+        const auto t0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipSetDevice(device));
+        {
+            // (the link's lock is not held together with the snapshot's: a snapshot is not
+            // freed while a call on it runs, only before or after)
+            const Snapshot *sp;
+            {
+                std::lock_guard<std::mutex> lk(link->mu);
+                sp = link->snap;
+            }
+            if (!sp) throw Error(KETOGPU_EINVAL, "reverse lookup: the snapshot was freed");
+            std::shared_lock<std::shared_mutex> rd(sp->mu);
+            if (sp->version != version) upload(*sp);
+        }
+        *needed = 0;
+        st.requests += n;
+        if (n) {
+            d_targets.need(n), d_ovf.need(n), d_begin.need(n), d_count.need(n), d_ctr.need(4), d_out.need(capacity);
+            HIP_CHECK(hipMemcpyAsync(d_targets.p, targets, n * 4, hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemsetAsync(d_ctr.p, 0, 4 * sizeof(unsigned long long), stream));
+            LOut o{d_out.p, capacity, d_begin.p, d_count.p, d_ctr.p, d_ctr.p + 1};
+            unsigned int *ovf_count = (unsigned int *)(d_ctr.p + 2);
+            KLAUNCH(lookup_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_targets.p, (uint32_t)n, type,
+                    force_tier2 ? 1 : 0, o, d_ovf.p, ovf_count);
+            unsigned long long ctr[4];
+            HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            const uint32_t ovf = (uint32_t)(ctr[2] & 0xFFFFFFFFu);
+            if (ovf) {
+                need_slots(ovf);
+                for (uint32_t first = 0; first < ovf; first += slots) {
+                    const uint32_t k = std::min<uint32_t>(slots, ovf - first);
+                    KLAUNCH(lookup_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_targets.p, type, o, d_ovf.p,
+                            first, d_bm.p, bm_words, d_wl.p);
+                    st.tier2_rounds++;
+                }
+                HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
+            }
+            HIP_CHECK(hipMemcpyAsync(begin, d_begin.p, n * 8, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(count, d_count.p, n * 8, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            const uint64_t written = std::min<uint64_t>(ctr[0], capacity);  // every written list ends below both
+            if (written && out) {
+                HIP_CHECK(hipMemcpyAsync(out, d_out.p, written * 4, hipMemcpyDeviceToHost, stream));
+                HIP_CHECK(hipStreamSynchronize(stream));
+            }
+            *needed = ctr[0];
+            st.tier2_requests += ovf;
+            uint64_t invalid = 0;
+            for (size_t i = 0; i < n; i++) invalid += begin[i] == KETOGPU_LOOKUP_INVALID || targets[i] == NONE;
+            st.tier1_requests += n - ovf - invalid;
+            st.ids_produced += ctr[0];
+            st.truncated_lists += ctr[1];
+        }
+        st.last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+
+    ~ketogpu_lookup() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+        d_off.drop(), d_col.drop(), d_type.drop(), d_targets.drop(), d_ovf.drop(), d_out.drop(), d_bm.drop(), d_wl.drop();
+        d_begin.drop(), d_count.drop(), d_ctr.drop();
+    }
+};
+
+namespace {
+
+template <class F>
+int guarded(F &&f) {
+    try {
+        f();
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ketogpu_lookup_new(const ketogpu_snapshot *sp, const ketogpu_lookup_opts *opts, ketogpu_lookup **out) {
+    if (!sp || !out) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *out = nullptr;
+    return guarded([&] {
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        auto l = std::make_unique<ketogpu_lookup>();
+        l->device = opts ? opts->device : 0;
+        l->budget = opts ? opts->state_budget_bytes : 0;
+        if (const char *e = getenv("KETOGPU_LOOKUP_TIER")) l->force_tier2 = atoi(e) == 2;
+        if (const char *e = getenv("KETOGPU_LOOKUP_SLOTS")) l->slot_cap = (uint32_t)std::max(atoi(e), 0);
+        l->st.set_capacity = kSetCap;
+        l->link = s.link;
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || l->device < 0 || l->device >= ndev)
+            throw Error(KETOGPU_EDEVICE, "reverse lookup: no such HIP device");
+        HIP_CHECK(hipSetDevice(l->device));
+        HIP_CHECK(hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
+        std::shared_lock<std::shared_mutex> rd(s.mu);
+        l->upload(s);
+        {
+            std::lock_guard<std::mutex> lk(s.link->mu);
+            s.link->snap = &s;  // the way back to the snapshot; its destructor clears it
+        }
+        *out = l.release();
+    });
+}
+
+void ketogpu_lookup_free(ketogpu_lookup *l) { delete l; }
+
+int ketogpu_lookup_stats_get(const ketogpu_lookup *l, ketogpu_lookup_stats *out) {
+    if (!l || !out) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    std::lock_guard<std::mutex> lk(const_cast<ketogpu_lookup *>(l)->mu);
+    *out = l->st;
+    return KETOGPU_OK;
+}
+
+int ketogpu_lookup_ids(ketogpu_lookup *l, const uint32_t *targets, size_t n, uint32_t type, uint32_t *out,
+                       uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
+    if (!l || !needed || (n && (!targets || !begin || !count)) || (capacity && !out)) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    if (n >= (1ull << 31)) {
+        set_last_error("reverse lookup: more than 2^31 - 1 targets in one call");
+        return KETOGPU_EINVAL;
+    }
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(l->mu);
+        l->run(targets, n, type, out, capacity, begin, count, needed);
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,132 @@
+// lookup_host.cpp — reverse lookup on the host (include/ketogpu.h "reverse lookup"):
+//   * the object types of the expandable nodes (lookup.hpp),
+//   * ketogpu_snapshot_type / ketogpu_snapshot_node: names <-> ids for callers that list,
+//   * ketogpu_snapshot_lookup: B(t) as a worklist closure over rev_off / rev_col.  DESIGN.md
+//     states the check contract as allowed(r, t) <=> r in B(t), B(t) the expandable nodes
+//     that reach t in >= 1 edge; listing B(t) answers the reverse question exactly.  Only
+//     interior entries (ids < Ni) have reverse rows, so only they are expanded.
+#include <unordered_set>
+
+#include "lookup.hpp"
+
+namespace ketogpu {
+
+std::shared_ptr<const TypeIndex> type_index_of(const Snapshot &s) {
+    std::lock_guard<std::mutex> lk(s.derived_mu);
+    if (s.type_cache && s.type_cache_version == s.version) return s.type_cache;
+    auto t = std::make_shared<TypeIndex>();
+    t->node_type.assign(s.Nx, KETOGPU_TYPE_NONE);
+    std::map<int32_t, bool> empty_ns;  // namespace id -> its configured name is ""
+    for (const Namespace &n : s.namespaces) empty_ns[n.id] = n.name.empty();
+    for (uint32_t v = 0; v < s.Nx; v++) {
+        if (v == s.Df || v == s.Dbi || v == s.Dbo || s.node_kind[v] != KETOGPU_SUBJECT_SET) continue;
+        auto e = empty_ns.find(s.node_ns[v]);
+        const bool wild = s.node_a[v] == 0 || s.node_b[v] == 0 || (e != empty_ns.end() && e->second);
+        auto key = std::make_tuple(s.node_ns[v], s.node_b[v], wild);
+        auto it = t->ids.find(key);
+        if (it == t->ids.end()) it = t->ids.emplace(key, (uint32_t)t->ids.size()).first;
+        t->node_type[v] = it->second;
+    }
+    s.type_cache = t;
+    s.type_cache_version = s.version;
+    return t;
+}
+
+}  // namespace ketogpu
+
+using namespace ketogpu;
+
+extern "C" {
+
+int ketogpu_snapshot_type(const ketogpu_snapshot *sp, const char *ns_name, const char *relation, uint32_t *type) {
+    if (!sp || !type) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+    std::shared_lock<std::shared_mutex> rd(s.mu);
+    *type = KETOGPU_TYPE_NONE;
+    std::string_view ns = sv(ns_name), rel = sv(relation);
+    if (ns.empty() || rel.empty()) return KETOGPU_OK;  // wildcard types are not addressable by name
+    const Namespace *n = s.ns_by_name(ns);
+    const uint32_t rid = s.pool.find(rel);
+    if (!n || rid == NONE) return KETOGPU_OK;
+    auto t = type_index_of(s);
+    auto it = t->ids.find(std::make_tuple(n->id, rid, false));
+    if (it != t->ids.end()) *type = it->second;
+    return KETOGPU_OK;
+}
+
+int ketogpu_snapshot_node(const ketogpu_snapshot *sp, uint32_t id, ketogpu_node_info *out) {
+    if (!sp || !out) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+    std::shared_lock<std::shared_mutex> rd(s.mu);
+    if (id >= s.N || id == s.Df || id == s.Dbi || id == s.Dbo) {
+        set_last_error(id >= s.N ? "node id outside the snapshot" : "placeholder node");
+        return KETOGPU_EINVAL;
+    }
+    *out = ketogpu_node_info{};
+    out->kind = s.node_kind[id];
+    out->expandable = id < s.Nx;
+    out->type = id < s.Nx ? type_index_of(s)->node_type[id] : KETOGPU_TYPE_NONE;
+    auto put = [](std::string_view v, const char *&p, size_t &n) { p = v.data(), n = v.size(); };
+    put(std::string_view("", 0), out->ns, out->ns_len);
+    put(std::string_view("", 0), out->rel, out->rel_len);
+    put(s.pool.get(s.node_a[id]), out->id, out->id_len);
+    if (out->kind == KETOGPU_SUBJECT_SET) {
+        out->namespace_id = s.node_ns[id];
+        if (const Namespace *n = s.ns_by_id(s.node_ns[id])) put(n->name, out->ns, out->ns_len);
+        put(s.pool.get(s.node_b[id]), out->rel, out->rel_len);
+    }
+    return KETOGPU_OK;
+}
+
+int ketogpu_snapshot_lookup(const ketogpu_snapshot *sp, uint32_t target, uint32_t type, uint32_t **ids, uint64_t *n) {
+    if (!sp || !ids || !n) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *ids = nullptr;
+    *n = 0;
+    try {
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        std::shared_lock<std::shared_mutex> rd(s.mu);
+        if (s.has_ambiguous)
+            throw Error(KETOGPU_EINVAL, "reverse lookup: the snapshot has shared Subject.String() keys (R4)");
+        if (target != NONE && target >= s.N) throw Error(KETOGPU_EINVAL, "target outside the snapshot");
+        std::vector<uint32_t> res;
+        if (target != NONE) {
+            auto types = type_index_of(s);
+            std::unordered_set<uint32_t> seen;
+            std::vector<uint32_t> work;
+            auto row = [&](uint32_t v) {
+                for (uint64_t j = s.rev_off[v]; j < s.rev_off[v + 1]; j++) {
+                    const uint32_t u = s.rev_col[j];
+                    if (!seen.insert(u).second) continue;
+                    if (u < s.Ni) work.push_back(u);
+                    if (u < s.Nx && type_matches(types->node_type[u], type)) res.push_back(u);
+                }
+            };
+            row(target);
+            for (size_t h = 0; h < work.size(); h++) row(work[h]);
+            std::sort(res.begin(), res.end());
+        }
+        uint32_t *p = (uint32_t *)malloc(std::max<size_t>(res.size(), 1) * sizeof(uint32_t));
+        if (!p) throw std::bad_alloc();
+        if (!res.empty()) memcpy(p, res.data(), res.size() * sizeof(uint32_t));
+        *ids = p;
+        *n = res.size();
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
+
+}  // extern "C"

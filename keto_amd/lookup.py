@@ -1,0 +1,135 @@
+"""Reverse lookup: every object a subject can reach (include/ketogpu.h ketogpu_lookup_*).
+
+"Which documents can this user view?" — OpenFGA's ListObjects, SpiceDB's LookupResources.
+lookup(t, T) is the set of expandable nodes r of object type T with SubjectIsAllowed(r, t):
+the backward closure B(t) over the snapshot's reverse rows (DESIGN.md "Reverse lookup").
+`host_lookup` walks the rows on the CPU; `Lookup` is the device handle (keto_amd/csrc/lookup.hip).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from . import persistence
+from .relationtuple import SubjectID, SubjectSet
+
+TYPE_ANY, TYPE_NONE = L.TYPE_ANY, L.TYPE_NONE
+TRUNCATED, INVALID = L.LOOKUP_TRUNCATED, L.LOOKUP_INVALID
+
+
+def host_lookup(snapshot, target, type_id=TYPE_ANY):
+    """ketogpu_snapshot_lookup: ascending node ids (uint32).  No GPU."""
+    p, n = C.c_void_p(), C.c_uint64()
+    lib = snapshot.L
+    L.check(lib.ketogpu_snapshot_lookup(snapshot.h, int(target), int(type_id), C.byref(p), C.byref(n)))
+    try:
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n.value,)).copy() if n.value \
+            else np.zeros(0, dtype=np.uint32)
+    finally:
+        lib.ketogpu_free(p)
+
+
+def resolve_subjects(snapshot, subjects):
+    """subjects (SubjectID / SubjectSet / their dict forms) -> target node ids (NODE_NONE for a
+    subject no tuple names)"""
+    if not len(subjects):
+        return np.zeros(0, dtype=np.uint32)
+    # the root side of the requests is unused: a concrete query that resolves without error
+    cols = persistence.request_columns([("-", "-", "-", s) for s in subjects])
+    _, targets, status = snapshot.resolve_batch(cols)
+    if (status == L.EINVAL).any():
+        raise L.KetoError(L.EINVAL, "subject is not allowed to be nil")
+    return targets.copy()
+
+
+class Lookup:
+    """device handle over a snapshot's reverse rows.  A write to a writable snapshot is seen by
+    the next call (the rows are uploaded again when the snapshot's version has moved)."""
+
+    def __init__(self, snapshot, device=0, state_budget_bytes=0):
+        self.L = L.lib()
+        self.snapshot = snapshot
+        opts = L.LookupOpts(device, state_budget_bytes)
+        h = C.c_void_p()
+        L.check(self.L.ketogpu_lookup_new(snapshot.h, C.byref(opts), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ketogpu_lookup_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def stats(self):
+        st = L.LookupStats()
+        L.check(self.L.ketogpu_lookup_stats_get(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def lookup_ids_raw(self, targets, type_id=TYPE_ANY, capacity=0):
+        """one ketogpu_lookup_ids call -> (out, begin, count, needed): count[i] exact, begin[i]
+        the offset of list i in out, or TRUNCATED / INVALID; capacity 0 only counts"""
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        n = len(targets)
+        out = np.empty(max(int(capacity), 1), dtype=np.uint32)
+        begin = np.empty(max(n, 1), dtype=np.uint64)
+        count = np.empty(max(n, 1), dtype=np.uint64)
+        needed = C.c_uint64()
+        L.check(self.L.ketogpu_lookup_ids(self.h, targets.ctypes.data, n, int(type_id),
+                                          out.ctypes.data if capacity else None, int(capacity), begin.ctypes.data,
+                                          count.ctypes.data, C.byref(needed)))
+        return out[:int(capacity)], begin[:n], count[:n], needed.value
+
+    def lookup_ids(self, targets, type_id=TYPE_ANY, capacity=None):
+        """-> one ascending uint32 array per target.  The first call uses `capacity` ids
+        (default 64 per target); only the targets whose lists were truncated are issued
+        again, with capacity = what they need.  An id outside the snapshot raises EINVAL."""
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        res = [None] * len(targets)
+        idx = np.arange(len(targets))
+        cap = 64 * len(targets) if capacity is None else int(capacity)
+        while len(idx):
+            out, begin, count, _ = self.lookup_ids_raw(targets[idx], type_id, cap)
+            if (begin == INVALID).any():
+                raise L.KetoError(L.EINVAL, f"target {int(targets[idx][begin == INVALID][0])} is outside the snapshot")
+            done = begin != TRUNCATED
+            for k in np.nonzero(done)[0]:
+                b, c = int(begin[k]), int(count[k])
+                res[idx[k]] = np.sort(out[b:b + c])
+            cap = int(count[~done].sum())  # exactly what the rest needs: nothing is truncated twice
+            idx = idx[~done]
+        return res
+
+    # ---- names
+    def _objects(self, ids):
+        return sorted(self.snapshot.node_info(int(v))["id"] for v in ids)
+
+    def list_objects_batch(self, namespace, relation, subjects):
+        """per subject: the sorted object names o with Check(namespace:o#relation@subject)"""
+        ty = self.snapshot.type_id(namespace, relation)
+        targets = resolve_subjects(self.snapshot, list(subjects))
+        if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
+            return [[] for _ in targets]
+        return [self._objects(ids) for ids in self.lookup_ids(targets, ty)]
+
+    def ListObjects(self, namespace, relation, subject):
+        return self.list_objects_batch(namespace, relation, [subject])[0]
+
+
+def host_list_objects(snapshot, namespace, relation, subject):
+    """ListObjects on the CPU (host_lookup)"""
+    ty = snapshot.type_id(namespace, relation)
+    t = int(resolve_subjects(snapshot, [subject])[0])
+    if ty == TYPE_NONE or t == L.NODE_NONE:
+        return []
+    return sorted(snapshot.node_info(int(v))["id"] for v in host_lookup(snapshot, t, ty))
+
+
+__all__ = ["Lookup", "host_lookup", "host_list_objects", "resolve_subjects", "TYPE_ANY", "TYPE_NONE", "TRUNCATED",
+           "INVALID", "SubjectID", "SubjectSet"]

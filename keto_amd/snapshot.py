@@ -226,6 +226,31 @@ class Snapshot:
         finally:
             self.L.ketogpu_label_index_free(h)
 
+    # ---- reverse lookup (keto_amd/lookup.py)
+    def type_id(self, namespace, relation):
+        """the object type of (namespace name, relation) for lookups (ketogpu_snapshot_type);
+        _lib.TYPE_NONE, which matches nothing, for an unknown namespace or an unused pair"""
+        t = C.c_uint32()
+        L.check(self.L.ketogpu_snapshot_type(self.h, L.b(namespace), L.b(relation), C.byref(t)))
+        return t.value
+
+    def node_info(self, node):
+        """ketogpu_snapshot_node as a dict: kind, namespace_id, type, expandable and the
+        decoded strings ns, id (object or subject id), rel"""
+        v = L.NodeInfo()
+        L.check(self.L.ketogpu_snapshot_node(self.h, int(node), C.byref(v)))
+        s = lambda p, n: C.string_at(p, n).decode("utf-8") if n else ""
+        return {"kind": v.kind, "namespace_id": v.namespace_id, "type": v.type, "expandable": bool(v.expandable),
+                "ns": s(v.ns, v.ns_len), "id": s(v.id, v.id_len), "rel": s(v.rel, v.rel_len)}
+
+    def describe(self, node):
+        """the subject a node id stands for: SubjectID or SubjectSet (KetoError EINVAL for an
+        id outside the snapshot or a writable snapshot's placeholder)"""
+        d = self.node_info(node)
+        if d["kind"] == L.SUBJECT_ID:
+            return SubjectID(d["id"])
+        return SubjectSet(d["ns"], d["id"], d["rel"])
+
     def resolve(self, namespace, obj, relation, subject):
         """-> (root, target) node ids (KETOGPU_NODE_NONE when absent)"""
         req = L.CheckRequest(L.b(namespace), L.b(obj), L.b(relation), subject_struct(subject))
