@@ -1017,6 +1017,79 @@ int ketogpu_lookup_stats_get(const ketogpu_lookup *l, ketogpu_lookup_stats *out)
 int ketogpu_lookup_ids(ketogpu_lookup *l, const uint32_t *targets, size_t n, uint32_t type, uint32_t *out,
                        uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
 
+/* ------------------------------------------------------- subject listing */
+/* "Who can reach this object?" (OpenFGA ListUsers, SpiceDB LookupSubjects).  For a root node r
+ * and a class C, subjects(r, C) is the set of nodes t of class C for which SubjectIsAllowed(r, t)
+ * is true, without duplicates: the forward closure F(r) = {t : r in B(t)} over the rows the
+ * check engine sees (page-poison truncated, R7; wildcard rows materialized, R5) — the least set
+ * that holds row(r) and row(x) for every interior x in it (DESIGN.md "Subject listing").  Its
+ * cost follows the answer.  r itself is listed only when a cycle leads back to it (R2); there is
+ * no depth cutoff.  Dynamic wildcard roots (queries without a snapshot node) are not nodes and
+ * cannot be listed.  Snapshots with shared Subject.String() keys (R4) are refused with
+ * KETOGPU_EINVAL, as in the reverse lookup.
+ *
+ * The CLASS of a node extends the reverse lookup's type to all num_nodes nodes: an expandable
+ * node's class is its type (placeholders: KETOGPU_TYPE_NONE, never listed); a never-expanded
+ * subject id is KETOGPU_CLASS_SUBJECT_ID; a never-expanded subject set (a group named as a
+ * subject that has no rows of its own) has the type id of its (namespace id, relation) pair if
+ * an expandable node defines that type, and KETOGPU_CLASS_UNTYPED_SET otherwise.  As a filter,
+ * KETOGPU_TYPE_ANY lists every class but NONE, KETOGPU_CLASS_SUBJECT_ID "which users", a type
+ * id "which groups#member"; KETOGPU_TYPE_NONE and KETOGPU_CLASS_UNTYPED_SET list nothing (an
+ * untyped set shows under ANY only).
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+#define KETOGPU_CLASS_SUBJECT_ID 0xFFFFFFFDu
+#define KETOGPU_CLASS_UNTYPED_SET 0xFFFFFFFCu
+/* the class of node `id`; KETOGPU_EINVAL for ids >= num_nodes */
+int ketogpu_snapshot_subject_class(const ketogpu_snapshot *s, uint32_t id, uint32_t *cls);
+/* subjects(root, cls) on the host, a worklist closure over the snapshot's rows: *ids ascending,
+ * *n its length; free *ids with ketogpu_free.  root KETOGPU_NODE_NONE (an unknown namespace, a
+ * query no tuple matches) and roots in [num_expandable, num_nodes) give the empty list; any
+ * other id >= num_nodes: KETOGPU_EINVAL.  Needs no GPU; the yardstick of ketogpu_subjects_ids. */
+int ketogpu_snapshot_subjects(const ketogpu_snapshot *s, uint32_t root, uint32_t cls, uint32_t **ids, uint64_t *n);
+
+/* The device side: a handle of its own over a compact copy of the forward rows (4 bytes per
+ * edge) and the class array in HBM.  Every call compares ketogpu_snapshot_version with the
+ * version it uploaded and uploads again when a ketogpu_snapshot_write moved it. */
+typedef struct ketogpu_subjects ketogpu_subjects;
+typedef struct {
+    int32_t device;              /* HIP device ordinal                                      */
+    uint64_t state_budget_bytes; /* HBM for tier 2's per-slot state; 0 = at most 1/8 of the
+                                    free HBM                                                */
+} ketogpu_subjects_opts;
+typedef struct {
+    uint64_t requests;       /* since creation: roots passed in                            */
+    uint64_t tier1_requests; /* answered by the one-wave LDS kernel                        */
+    uint64_t tier2_requests; /* answered by the workgroup-per-request kernel               */
+    uint64_t tier2_rounds;   /* tier-2 launches (each serves up to `slots` requests)       */
+    uint64_t list_finishes;  /* tier 2: closures within list_capacity, finished by walking
+                                the seen list                                              */
+    uint64_t scan_finishes;  /* tier 2: larger closures, finished by scanning the bitmap    */
+    uint64_t ids_produced;   /* sum of the exact list sizes                                */
+    uint64_t truncated_lists;
+    uint64_t uploads;        /* row uploads (1 at creation, +1 per version change seen)    */
+    uint32_t set_capacity;   /* tier 1: nodes F(r) may hold before the request moves on    */
+    uint32_t slots;          /* tier 2: requests per round (0 before the first round)      */
+    uint32_t list_capacity;  /* tier 2: entries of a slot's seen list                      */
+    double last_call_ms;     /* host wall time of the last ketogpu_subjects_ids            */
+} ketogpu_subjects_stats;
+/* Environment, read here: KETOGPU_SUBJECTS_TIER=2 sends every request to tier 2;
+ * KETOGPU_SUBJECTS_SLOTS=k caps tier 2's slots; KETOGPU_SUBJECTS_LIST_CAP=k sets list_capacity
+ * (0: every tier-2 request finishes by scan). */
+int ketogpu_subjects_new(const ketogpu_snapshot *s, const ketogpu_subjects_opts *opts, ketogpu_subjects **out);
+void ketogpu_subjects_free(ketogpu_subjects *h);
+int ketogpu_subjects_stats_get(const ketogpu_subjects *h, ketogpu_subjects_stats *out);
+/* subjects(roots[i], cls) for n roots in one call.  The output contract is that of
+ * ketogpu_lookup_ids: count[i] is always the exact size of list i; begin[i] is the offset in
+ * `out` of list i, written completely, or KETOGPU_LOOKUP_TRUNCATED (the list did not fit in
+ * `capacity` ids; nothing of it was written) or KETOGPU_LOOKUP_INVALID (roots[i] >= num_nodes
+ * and not KETOGPU_NODE_NONE; count 0).  *needed = the sum of all counts; needed <= capacity
+ * guarantees that nothing was truncated (every request reserves exactly count[i] ids).  Lists
+ * lie in `out` in any order, the ids inside a list in any order, without duplicates.
+ * capacity 0 with out NULL is the count-only call.  Returns KETOGPU_OK also when lists were
+ * truncated. */
+int ketogpu_subjects_ids(ketogpu_subjects *h, const uint32_t *roots, size_t n, uint32_t cls, uint32_t *out,
+                         uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

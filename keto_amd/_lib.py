@@ -23,6 +23,8 @@ WRITE_REASONS = {0: "applied", 1: "not_writable", 2: "wildcard", 3: "poison", 4:
 NODE_UNION, NODE_LEAF = 0, 1
 TYPE_ANY, TYPE_NONE = 0xFFFFFFFF, 0xFFFFFFFE  # reverse lookup: no type filter / matches nothing
 LOOKUP_TRUNCATED, LOOKUP_INVALID = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE
+# subject listing: classes beyond the type ids (a never-expanded subject id / subject set without a type)
+CLASS_SUBJECT_ID, CLASS_UNTYPED_SET = 0xFFFFFFFD, 0xFFFFFFFC
 
 
 class KetoError(Exception):
@@ -322,6 +324,22 @@ class LookupStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# include/ketogpu.h subject listing
+class SubjectsOpts(C.Structure):
+    _fields_ = [("device", C.c_int32), ("state_budget_bytes", C.c_uint64)]
+
+
+class SubjectsStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "requests", "tier1_requests", "tier2_requests", "tier2_rounds", "list_finishes", "scan_finishes",
+        "ids_produced", "truncated_lists", "uploads")] + [
+            ("set_capacity", C.c_uint32), ("slots", C.c_uint32), ("list_capacity", C.c_uint32),
+            ("last_call_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol declared in include/ketogpu.h, with its ctypes signature
 vp, i32, u32, sz = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t
 SIGNATURES = {
@@ -449,6 +467,12 @@ SIGNATURES = {
     "ketogpu_lookup_free": (None, [vp]),
     "ketogpu_lookup_stats_get": (C.c_int, [vp, C.POINTER(LookupStats)]),
     "ketogpu_lookup_ids": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_snapshot_subject_class": (C.c_int, [vp, u32, C.POINTER(u32)]),
+    "ketogpu_snapshot_subjects": (C.c_int, [vp, u32, u32, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+    "ketogpu_subjects_new": (C.c_int, [vp, C.POINTER(SubjectsOpts), C.POINTER(vp)]),
+    "ketogpu_subjects_free": (None, [vp]),
+    "ketogpu_subjects_stats_get": (C.c_int, [vp, C.POINTER(SubjectsStats)]),
+    "ketogpu_subjects_ids": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

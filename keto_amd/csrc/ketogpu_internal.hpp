@@ -139,6 +139,7 @@ struct RowRef {
 
 struct ReachLabels;  // labels.hpp
 struct TypeIndex;    // lookup.hpp
+struct ClassIndex;   // subjects.hpp
 
 struct Snapshot {
     // ---- configuration
@@ -235,6 +236,9 @@ struct Snapshot {
     // reverse lookup's per-node object types (lookup.hpp type_index_of), derived per version
     mutable std::shared_ptr<const TypeIndex> type_cache;
     mutable uint64_t type_cache_version = ~0ull;
+    // subject listing's per-node classes (subjects.hpp class_index_of), derived per version
+    mutable std::shared_ptr<const ClassIndex> class_cache;
+    mutable uint64_t class_cache_version = ~0ull;
     // An engine's way back to its snapshot at teardown: the snapshot's destructor clears it,
     // so an engine freed after its snapshot (a garbage collector's order) skips the
     // deregistration instead of touching freed memory.

@@ -26,6 +26,7 @@
 #include <chrono>
 #include <cstdlib>
 
+#include "hip_host.hpp"
 #include "lookup.hpp"
 
 using namespace ketogpu;
@@ -219,41 +220,6 @@ __global__ __launch_bounds__(kT2Block) void lookup_tier2_kernel(LGraph g, const 
     }
 }
 
-#define HIP_CHECK(x)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (x);                                                                           \
-        if (_e != hipSuccess)                                                                          \
-            throw Error(KETOGPU_EDEVICE, std::string(#x) + ": " + hipGetErrorString(_e));              \
-    } while (0)
-
-// every launch is checked: a failed launch must fail its call, not a later one
-#define KLAUNCH(...)                                 \
-    do {                                             \
-        hipLaunchKernelGGL(__VA_ARGS__);             \
-        HIP_CHECK(hipGetLastError());                \
-    } while (0)
-
-// a device array that only grows
-template <class T>
-struct DBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    void need(size_t n) {
-        if (n <= cap && p) return;
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
-        void *q = nullptr;
-        n = std::max<size_t>(n, 1);
-        hipError_t e = hipMalloc(&q, n * sizeof(T));
-        if (e != hipSuccess) throw Error(KETOGPU_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-        p = (T *)q, cap = n;
-    }
-    void drop() {
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
-    }
-};
-
 }  // namespace
 
 struct ketogpu_lookup {
@@ -387,24 +353,6 @@ struct ketogpu_lookup {
         d_begin.drop(), d_count.drop(), d_ctr.drop();
     }
 };
-
-namespace {
-
-template <class F>
-int guarded(F &&f) {
-    try {
-        f();
-        return KETOGPU_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_last_error("out of host memory");
-        return KETOGPU_ENOMEM;
-    }
-}
-
-}  // namespace
 
 extern "C" {
 

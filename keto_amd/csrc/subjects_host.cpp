@@ -1,0 +1,107 @@
+// subjects_host.cpp — subject listing on the host (include/ketogpu.h "subject listing"):
+//   * the classes of all nodes (subjects.hpp),
+//   * ketogpu_snapshot_subject_class,
+//   * ketogpu_snapshot_subjects: F(r) as a worklist closure over node_row.  DESIGN.md states
+//     the check contract as allowed(r, t) <=> r in B(t); F(r) = {t : r in B(t)} is the set of
+//     nodes reached from r in >= 1 edge over the rows the check engine sees (the first `len`
+//     entries of each row).  Only interior entries (ids < Ni) are expanded: nodes in [Ni, Nx)
+//     appear in no row and nodes from Nx on have no rows.
+#include <unordered_set>
+
+#include "subjects.hpp"
+
+namespace ketogpu {
+
+std::shared_ptr<const ClassIndex> class_index_of(const Snapshot &s) {
+    auto types = type_index_of(s);  // (takes derived_mu itself)
+    std::lock_guard<std::mutex> lk(s.derived_mu);
+    if (s.class_cache && s.class_cache_version == s.version) return s.class_cache;
+    auto c = std::make_shared<ClassIndex>();
+    c->node_class.assign(s.N, KETOGPU_TYPE_NONE);
+    std::copy(types->node_type.begin(), types->node_type.end(), c->node_class.begin());
+    std::map<int32_t, bool> empty_ns;  // namespace id -> its configured name is ""
+    for (const Namespace &n : s.namespaces) empty_ns[n.id] = n.name.empty();
+    for (uint32_t v = s.Nx; v < s.N; v++) {
+        if (s.node_kind[v] != KETOGPU_SUBJECT_SET) {
+            c->node_class[v] = KETOGPU_CLASS_SUBJECT_ID;
+            continue;
+        }
+        auto e = empty_ns.find(s.node_ns[v]);
+        const bool wild = s.node_a[v] == 0 || s.node_b[v] == 0 || (e != empty_ns.end() && e->second);
+        auto it = types->ids.find(std::make_tuple(s.node_ns[v], s.node_b[v], wild));
+        c->node_class[v] = it != types->ids.end() ? it->second : KETOGPU_CLASS_UNTYPED_SET;
+    }
+    s.class_cache = c;
+    s.class_cache_version = s.version;
+    return c;
+}
+
+}  // namespace ketogpu
+
+using namespace ketogpu;
+
+extern "C" {
+
+int ketogpu_snapshot_subject_class(const ketogpu_snapshot *sp, uint32_t id, uint32_t *cls) {
+    if (!sp || !cls) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+    std::shared_lock<std::shared_mutex> rd(s.mu);
+    *cls = KETOGPU_TYPE_NONE;
+    if (id >= s.N) {
+        set_last_error("node id outside the snapshot");
+        return KETOGPU_EINVAL;
+    }
+    *cls = class_index_of(s)->node_class[id];
+    return KETOGPU_OK;
+}
+
+int ketogpu_snapshot_subjects(const ketogpu_snapshot *sp, uint32_t root, uint32_t cls, uint32_t **ids, uint64_t *n) {
+    if (!sp || !ids || !n) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *ids = nullptr;
+    *n = 0;
+    try {
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        std::shared_lock<std::shared_mutex> rd(s.mu);
+        if (s.has_ambiguous)
+            throw Error(KETOGPU_EINVAL, "subject listing: the snapshot has shared Subject.String() keys (R4)");
+        if (root != NONE && root >= s.N) throw Error(KETOGPU_EINVAL, "root outside the snapshot");
+        std::vector<uint32_t> res;
+        if (root < s.Nx) {  // (NONE and the never-expanded nodes: the empty list)
+            auto classes = class_index_of(s);
+            std::unordered_set<uint32_t> seen;
+            std::vector<uint32_t> work;
+            auto row = [&](uint32_t v) {
+                const uint32_t *p = s.row_ptr(v);
+                for (uint32_t j = 0; j < s.node_row[v].len; j++) {
+                    const uint32_t u = p[j];
+                    if (u >= s.N || !seen.insert(u).second) continue;
+                    if (u < s.Ni) work.push_back(u);
+                    if (class_matches(classes->node_class[u], cls)) res.push_back(u);
+                }
+            };
+            row(root);
+            for (size_t h = 0; h < work.size(); h++) row(work[h]);
+            std::sort(res.begin(), res.end());
+        }
+        uint32_t *p = (uint32_t *)malloc(std::max<size_t>(res.size(), 1) * sizeof(uint32_t));
+        if (!p) throw std::bad_alloc();
+        if (!res.empty()) memcpy(p, res.data(), res.size() * sizeof(uint32_t));
+        *ids = p;
+        *n = res.size();
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
+
+}  // extern "C"

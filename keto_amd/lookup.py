@@ -1,9 +1,16 @@
-"""Reverse lookup: every object a subject can reach (include/ketogpu.h ketogpu_lookup_*).
+"""Reverse lookup and subject listing: every object a subject can reach (include/ketogpu.h
+ketogpu_lookup_*), every subject that can reach an object (ketogpu_subjects_*).
 
 "Which documents can this user view?" — OpenFGA's ListObjects, SpiceDB's LookupResources.
 lookup(t, T) is the set of expandable nodes r of object type T with SubjectIsAllowed(r, t):
 the backward closure B(t) over the snapshot's reverse rows (DESIGN.md "Reverse lookup").
 `host_lookup` walks the rows on the CPU; `Lookup` is the device handle (keto_amd/csrc/lookup.hip).
+
+"Who can view this document?" — OpenFGA's ListUsers, SpiceDB's LookupSubjects.
+subjects(r, C) is the set of nodes t of class C with SubjectIsAllowed(r, t): the forward
+closure F(r) over the rows the check engine sees (DESIGN.md "Subject listing").
+`host_subjects` walks the rows on the CPU; `Subjects` is the device handle
+(keto_amd/csrc/subjects.hip).
 """
 import ctypes as C
 
@@ -15,6 +22,7 @@ from .relationtuple import SubjectID, SubjectSet
 
 TYPE_ANY, TYPE_NONE = L.TYPE_ANY, L.TYPE_NONE
 TRUNCATED, INVALID = L.LOOKUP_TRUNCATED, L.LOOKUP_INVALID
+CLASS_SUBJECT_ID, CLASS_UNTYPED_SET = L.CLASS_SUBJECT_ID, L.CLASS_UNTYPED_SET
 
 
 def host_lookup(snapshot, target, type_id=TYPE_ANY):
@@ -131,5 +139,143 @@ def host_list_objects(snapshot, namespace, relation, subject):
     return sorted(snapshot.node_info(int(v))["id"] for v in host_lookup(snapshot, t, ty))
 
 
-__all__ = ["Lookup", "host_lookup", "host_list_objects", "resolve_subjects", "TYPE_ANY", "TYPE_NONE", "TRUNCATED",
-           "INVALID", "SubjectID", "SubjectSet"]
+def host_subjects(snapshot, root, cls=TYPE_ANY):
+    """ketogpu_snapshot_subjects: ascending node ids (uint32).  No GPU."""
+    p, n = C.c_void_p(), C.c_uint64()
+    lib = snapshot.L
+    L.check(lib.ketogpu_snapshot_subjects(snapshot.h, int(root), int(cls), C.byref(p), C.byref(n)))
+    try:
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n.value,)).copy() if n.value \
+            else np.zeros(0, dtype=np.uint32)
+    finally:
+        lib.ketogpu_free(p)
+
+
+def resolve_roots(snapshot, objects):
+    """(namespace, object, relation) triples -> root node ids (NODE_NONE for an unknown
+    namespace or a query no tuple matches).  A wildcard query without a snapshot node (a
+    dynamic root) cannot be listed and raises KetoError(EINVAL)."""
+    if not len(objects):
+        return np.zeros(0, dtype=np.uint32)
+    # the subject side of the requests is unused: any non-nil subject resolves without error
+    cols = persistence.request_columns([(ns, obj, rel, {"subject_id": "-"}) for ns, obj, rel in objects])
+    roots, _, status = snapshot.resolve_batch(cols)
+    if (status == L.ENOTFOUND).any():
+        ns, obj, rel = objects[int(np.nonzero(status == L.ENOTFOUND)[0][0])]
+        raise L.KetoError(L.EINVAL, f"{ns}:{obj}#{rel} is a wildcard query without a node: its subjects cannot be "
+                                    "listed")
+    return roots.copy()
+
+
+def _class_of_kind(snapshot, kind):
+    """kind "ids" / "any" / (namespace, relation) -> class filter"""
+    if isinstance(kind, str):
+        if kind == "ids":
+            return CLASS_SUBJECT_ID
+        if kind == "any":
+            return TYPE_ANY
+        raise ValueError(f"kind {kind!r}: expected 'ids', 'any' or a (namespace, relation) pair")
+    namespace, relation = kind
+    return snapshot.type_id(namespace, relation)  # TYPE_NONE for a pair without a type id: nothing
+
+
+def _subjects_of(snapshot, ids):
+    """node ids -> SubjectIDs, then SubjectSets, each sorted"""
+    subs = [snapshot.describe(int(v)) for v in ids]
+    users = sorted((s for s in subs if isinstance(s, SubjectID)), key=lambda s: s.id)
+    sets = sorted((s for s in subs if isinstance(s, SubjectSet)), key=lambda s: (s.namespace, s.object, s.relation))
+    return users + sets
+
+
+class Subjects:
+    """device handle over a snapshot's forward rows.  A write to a writable snapshot is seen by
+    the next call (the rows are uploaded again when the snapshot's version has moved)."""
+
+    def __init__(self, snapshot, device=0, state_budget_bytes=0):
+        self.L = L.lib()
+        self.snapshot = snapshot
+        opts = L.SubjectsOpts(device, state_budget_bytes)
+        h = C.c_void_p()
+        L.check(self.L.ketogpu_subjects_new(snapshot.h, C.byref(opts), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ketogpu_subjects_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def stats(self):
+        st = L.SubjectsStats()
+        L.check(self.L.ketogpu_subjects_stats_get(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def subject_ids_raw(self, roots, cls=TYPE_ANY, capacity=0):
+        """one ketogpu_subjects_ids call -> (out, begin, count, needed): count[i] exact, begin[i]
+        the offset of list i in out, or TRUNCATED / INVALID; capacity 0 only counts"""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        n = len(roots)
+        out = np.empty(max(int(capacity), 1), dtype=np.uint32)
+        begin = np.empty(max(n, 1), dtype=np.uint64)
+        count = np.empty(max(n, 1), dtype=np.uint64)
+        needed = C.c_uint64()
+        L.check(self.L.ketogpu_subjects_ids(self.h, roots.ctypes.data, n, int(cls),
+                                            out.ctypes.data if capacity else None, int(capacity), begin.ctypes.data,
+                                            count.ctypes.data, C.byref(needed)))
+        return out[:int(capacity)], begin[:n], count[:n], needed.value
+
+    def subject_ids(self, roots, cls=TYPE_ANY, capacity=None):
+        """-> one ascending uint32 array per root.  The first call uses `capacity` ids (default
+        64 per root); only the roots whose lists were truncated are issued again, with
+        capacity = what they need.  An id outside the snapshot raises EINVAL."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        res = [None] * len(roots)
+        idx = np.arange(len(roots))
+        cap = 64 * len(roots) if capacity is None else int(capacity)
+        while len(idx):
+            out, begin, count, _ = self.subject_ids_raw(roots[idx], cls, cap)
+            if (begin == INVALID).any():
+                raise L.KetoError(L.EINVAL, f"root {int(roots[idx][begin == INVALID][0])} is outside the snapshot")
+            done = begin != TRUNCATED
+            for k in np.nonzero(done)[0]:
+                b, c = int(begin[k]), int(count[k])
+                res[idx[k]] = np.sort(out[b:b + c])
+            cap = int(count[~done].sum())  # exactly what the rest needs: nothing is truncated twice
+            idx = idx[~done]
+        return res
+
+    # ---- names
+    def list_subjects_batch(self, roots, kind="ids"):
+        """per (namespace, object, relation) root: the subjects s with Check(root@s), SubjectIDs
+        then SubjectSets, each sorted.  kind: "ids" (subject ids only), "any", or a
+        (namespace, relation) pair (subject sets of that type; an unknown pair lists nothing)"""
+        roots = list(roots)
+        cls = _class_of_kind(self.snapshot, kind)
+        ids = resolve_roots(self.snapshot, roots)
+        if cls == TYPE_NONE:
+            return [[] for _ in roots]
+        return [_subjects_of(self.snapshot, v) for v in self.subject_ids(ids, cls)]
+
+    def ListSubjects(self, namespace, object, relation, kind="ids"):
+        return self.list_subjects_batch([(namespace, object, relation)], kind)[0]
+
+
+def host_list_subjects(snapshot, namespace, object, relation, kind="ids"):
+    """ListSubjects on the CPU (host_subjects)"""
+    cls = _class_of_kind(snapshot, kind)
+    r = int(resolve_roots(snapshot, [(namespace, object, relation)])[0])
+    if cls == TYPE_NONE or r == L.NODE_NONE:
+        return []
+    return _subjects_of(snapshot, host_subjects(snapshot, r, cls))
+
+
+__all__ = ["Lookup", "host_lookup", "host_list_objects", "resolve_subjects", "Subjects", "host_subjects",
+           "host_list_subjects", "resolve_roots", "TYPE_ANY", "TYPE_NONE", "CLASS_SUBJECT_ID", "CLASS_UNTYPED_SET",
+           "TRUNCATED", "INVALID", "SubjectID", "SubjectSet"]

@@ -243,6 +243,13 @@ class Snapshot:
         return {"kind": v.kind, "namespace_id": v.namespace_id, "type": v.type, "expandable": bool(v.expandable),
                 "ns": s(v.ns, v.ns_len), "id": s(v.id, v.id_len), "rel": s(v.rel, v.rel_len)}
 
+    def subject_class(self, node):
+        """the class of a node for subject listing (ketogpu_snapshot_subject_class): its type id,
+        _lib.CLASS_SUBJECT_ID, _lib.CLASS_UNTYPED_SET, or _lib.TYPE_NONE for a placeholder"""
+        c = C.c_uint32()
+        L.check(self.L.ketogpu_snapshot_subject_class(self.h, int(node), C.byref(c)))
+        return c.value
+
     def describe(self, node):
         """the subject a node id stands for: SubjectID or SubjectSet (KetoError EINVAL for an
         id outside the snapshot or a writable snapshot's placeholder)"""
