@@ -1090,6 +1090,46 @@ int ketogpu_subjects_stats_get(const ketogpu_subjects *h, ketogpu_subjects_stats
 int ketogpu_subjects_ids(ketogpu_subjects *h, const uint32_t *roots, size_t n, uint32_t cls, uint32_t *out,
                          uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
 
+/* ------------------------------------------------------- sorted, paged lists */
+/* One page of lookup(targets[i], type) / subjects(roots[i], cls) per request, selected in
+ * order on the device (Keto's list convention: page_size / page_token in, next_page_token out).
+ * M(i) is the member set of request i exactly as ketogpu_lookup_ids / ketogpu_subjects_ids
+ * define it: the filters, KETOGPU_NODE_NONE, never-expanded roots, placeholders and the R4
+ * refusal all behave the same.
+ *
+ *   from         inclusive lower bounds; NULL means 0 for every request
+ *   count[i]     = |M(i)|, exact, whatever from[i] is
+ *   remaining[i] = |{m in M(i) : m >= from[i]}|
+ *   returned[i]  = min(limit, remaining[i])
+ *   out[i * limit .. i * limit + returned[i])  the returned[i] smallest members >= from[i],
+ *                strictly ascending; the words of a stride past returned[i] are not to be read
+ *
+ * More pages exist exactly when remaining[i] > returned[i]; the next page starts at from =
+ * last id + 1.  Any from >= num_nodes is legal and gives remaining 0.  An id outside the
+ * snapshot (>= num_nodes and not KETOGPU_NODE_NONE) gives returned[i] = KETOGPU_PAGE_INVALID and
+ * count = remaining = 0; the call still returns KETOGPU_OK.  limit 0, limit >
+ * KETOGPU_PAGE_LIMIT_MAX, a null argument with n > 0 and n >= 2^31 give KETOGPU_EINVAL; n == 0
+ * is KETOGPU_OK.  There is no truncation protocol: the stride is the reservation.
+ *
+ * THE ORDER IS BY NODE ID, not by name.  It is total, and stable for the life of a snapshot
+ * object, in-place ketogpu_snapshot_write included (node ids never move; new subjects get
+ * reserved ids), so a page token — the next `from` — stays meaningful between calls.
+ *
+ * The handle behaves as for the full-list calls (re-upload when ketogpu_snapshot_version has
+ * moved, KETOGPU_EINVAL after the snapshot is freed, one call at a time, the same tier knobs),
+ * and paged requests count into the same stats: requests, tier1_requests, tier2_requests,
+ * tier2_rounds (and list_finishes / scan_finishes: how the slot was counted and cleared) as
+ * for the full-list calls, ids_produced += the sum of returned; truncated_lists never moves.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+#define KETOGPU_PAGE_LIMIT_MAX 65536u
+#define KETOGPU_PAGE_INVALID 0xFFFFFFFFu /* in returned[i] */
+int ketogpu_lookup_page(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *from, size_t n, uint32_t type,
+                        uint32_t limit, uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
+                        uint64_t *remaining);
+int ketogpu_subjects_page(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *from, size_t n, uint32_t cls,
+                          uint32_t limit, uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
+                          uint64_t *remaining);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

@@ -25,6 +25,8 @@ TYPE_ANY, TYPE_NONE = 0xFFFFFFFF, 0xFFFFFFFE  # reverse lookup: no type filter /
 LOOKUP_TRUNCATED, LOOKUP_INVALID = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE
 # subject listing: classes beyond the type ids (a never-expanded subject id / subject set without a type)
 CLASS_SUBJECT_ID, CLASS_UNTYPED_SET = 0xFFFFFFFD, 0xFFFFFFFC
+# paged lists: the largest page / returned[i] for an id outside the snapshot
+PAGE_LIMIT_MAX, PAGE_INVALID = 65536, 0xFFFFFFFF
 
 
 class KetoError(Exception):
@@ -473,6 +475,8 @@ SIGNATURES = {
     "ketogpu_subjects_free": (None, [vp]),
     "ketogpu_subjects_stats_get": (C.c_int, [vp, C.POINTER(SubjectsStats)]),
     "ketogpu_subjects_ids": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_page": (C.c_int, [vp, vp, vp, sz, u32, u32, vp, vp, vp, vp]),
+    "ketogpu_subjects_page": (C.c_int, [vp, vp, vp, sz, u32, u32, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -19,6 +19,11 @@
 // it fits below `capacity` (else begin = TRUNCATED; the count is exact either way).  The cursor
 // ends at the sum of the counts, so a capacity of at least that sum truncates nothing.
 //
+// The paged call (ketogpu_lookup_page) runs the same two closures (tier1_closure, tier2_closure: one
+// implementation each, called by the full-list and the paged kernel) and ends with the ordered
+// finish of paged_finish.hpp instead: the `limit` smallest members >= from[i] to the stride
+// out + i * limit, ascending, with the exact count and what remains; no cursor, no truncation.
+//
 // Every index is validated before it is used: targets against num_nodes before rev_off is
 // touched, row entries against num_expandable before the type array or a bitmap is.
 #include <hip/hip_runtime.h>
@@ -28,6 +33,7 @@
 
 #include "hip_host.hpp"
 #include "lookup.hpp"
+#include "paged_finish.hpp"
 
 using namespace ketogpu;
 
@@ -37,6 +43,7 @@ constexpr uint32_t kSetCap = 1024;         // tier 1: nodes a set may hold (keto
 constexpr uint32_t kSlotsLds = 2 * kSetCap;  // hash slots: a load of at most (kSetCap + 64) / kSlotsLds
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 constexpr unsigned kT2Block = 256;
+static_assert(kT2Block == paged::kBlock, "the paged selection assumes tier 2's workgroup");
 
 struct LGraph {
     const uint64_t *rev_off;   // N + 1 (a writable snapshot: n_cap + 1)
@@ -63,25 +70,10 @@ __device__ inline uint32_t slot_of(uint32_t u) { return (u * 0x9E3779B1u) >> 21;
 static_assert(kSlotsLds == 1u << 11, "slot_of yields 11 bits");
 
 // ---------------------------------------------------------------------- tier 1
-__global__ __launch_bounds__(64) void lookup_tier1_kernel(LGraph g, const uint32_t *targets, uint32_t n, uint32_t type,
-                                                          int force_tier2, LOut o, uint32_t *ovf_list,
-                                                          unsigned int *ovf_count) {
-    __shared__ uint32_t set[kSlotsLds];
-    __shared__ uint32_t work[kSetCap + 64];
-    const uint32_t i = blockIdx.x, lane = threadIdx.x;
-    if (i >= n) return;
-    const uint32_t t = targets[i];
-    if (t >= g.N) {  // NONE: the empty list; any other id outside the snapshot: INVALID
-        if (lane == 0) {
-            o.begin[i] = t == KETOGPU_NODE_NONE ? 0ull : KETOGPU_LOOKUP_INVALID;
-            o.count[i] = 0;
-        }
-        return;
-    }
-    if (force_tier2) {
-        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
-        return;
-    }
+// tier 1's closure, by one wave: B(t) into `set` (all kSlotsLds slots are initialised here), its
+// interior members through `work`.  False when the set passed kSetCap: the request overflows.
+__device__ __forceinline__ bool tier1_closure(const LGraph &g, uint32_t t, uint32_t lane, uint32_t *set,
+                                              uint32_t *work) {
     for (uint32_t s = lane; s < kSlotsLds; s += 64) set[s] = kEmpty;
     __syncthreads();
     uint32_t size = 0, head = 0, tail = 0;  // wave-uniform
@@ -116,6 +108,29 @@ __global__ __launch_bounds__(64) void lookup_tier1_kernel(LGraph g, const uint32
         if (over || head == tail) break;
         v = work[head++];
     }
+    return !over;
+}
+
+__global__ __launch_bounds__(64) void lookup_tier1_kernel(LGraph g, const uint32_t *targets, uint32_t n, uint32_t type,
+                                                          int force_tier2, LOut o, uint32_t *ovf_list,
+                                                          unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = targets[i];
+    if (t >= g.N) {  // NONE: the empty list; any other id outside the snapshot: INVALID
+        if (lane == 0) {
+            o.begin[i] = t == KETOGPU_NODE_NONE ? 0ull : KETOGPU_LOOKUP_INVALID;
+            o.count[i] = 0;
+        }
+        return;
+    }
+    if (force_tier2) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    const bool over = !tier1_closure(g, t, lane, set, work);
     if (over) {
         if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
         return;
@@ -143,6 +158,37 @@ __global__ __launch_bounds__(64) void lookup_tier1_kernel(LGraph g, const uint32
 }
 
 // ---------------------------------------------------------------------- tier 2
+// tier 2's closure, by the whole workgroup: B(t) into the slot's bitmap `bm` (all zero on entry),
+// its interior members through the worklist `wl`.  *s_tail is an LDS counter, zero on entry and
+// published by a barrier.  Ends behind a barrier: every thread sees the whole bitmap.
+__device__ __forceinline__ void tier2_closure(const LGraph &g, uint32_t t, uint32_t *bm, uint32_t *wl,
+                                              unsigned int *s_tail) {
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = kT2Block / 64;
+    auto visit = [&](uint32_t u) {
+        if (u >= g.Nx) return;
+        const uint32_t bit = 1u << (u & 31);
+        if (atomicOr(&bm[u >> 5], bit) & bit) return;
+        if (u < g.Ni) wl[atomicAdd(s_tail, 1u)] = u;  // each interior node enters once: <= Ni entries
+    };
+    {  // the target's own row, by the whole workgroup
+        const uint64_t b = g.rev_off[t], e = g.rev_off[t + 1];
+        for (uint64_t j = b + tid; j < e; j += kT2Block) visit(g.rev_col[j]);
+    }
+    __syncthreads();
+    uint32_t lb = 0, le = *s_tail;
+    while (lb < le) {  // one level: a wave per row
+        __syncthreads();  // everyone has read s_tail before it moves
+        for (uint32_t k = lb + wave; k < le; k += nwaves) {
+            const uint32_t v = wl[k];
+            const uint64_t b = g.rev_off[v], e = g.rev_off[v + 1];
+            for (uint64_t j = b + lane; j < e; j += 64) visit(g.rev_col[j]);
+        }
+        __syncthreads();
+        lb = le;
+        le = *s_tail;
+    }
+}
+
 // Block s of round r serves overflow request ovf_list[first + s] with slot s's state.  The
 // bitmap is all zero on entry and is cleared again on the way out.
 __global__ __launch_bounds__(kT2Block) void lookup_tier2_kernel(LGraph g, const uint32_t *targets, uint32_t type,
@@ -154,33 +200,11 @@ __global__ __launch_bounds__(kT2Block) void lookup_tier2_kernel(LGraph g, const 
     const uint32_t t = targets[i];
     uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
     uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = kT2Block / 64;
+    const unsigned tid = threadIdx.x;
     if (tid == 0) s_tail = 0, s_cnt = 0, s_pos = 0;
     __syncthreads();
     if (t >= g.N) return;  // (tier 1 lists valid targets only)
-    auto visit = [&](uint32_t u) {
-        if (u >= g.Nx) return;
-        const uint32_t bit = 1u << (u & 31);
-        if (atomicOr(&bm[u >> 5], bit) & bit) return;
-        if (u < g.Ni) wl[atomicAdd(&s_tail, 1u)] = u;  // each interior node enters once: <= Ni entries
-    };
-    {  // the target's own row, by the whole workgroup
-        const uint64_t b = g.rev_off[t], e = g.rev_off[t + 1];
-        for (uint64_t j = b + tid; j < e; j += kT2Block) visit(g.rev_col[j]);
-    }
-    __syncthreads();
-    uint32_t lb = 0, le = s_tail;
-    while (lb < le) {  // one level: a wave per row
-        __syncthreads();  // everyone has read s_tail before it moves
-        for (uint32_t k = lb + wave; k < le; k += nwaves) {
-            const uint32_t v = wl[k];
-            const uint64_t b = g.rev_off[v], e = g.rev_off[v + 1];
-            for (uint64_t j = b + lane; j < e; j += 64) visit(g.rev_col[j]);
-        }
-        __syncthreads();
-        lb = le;
-        le = s_tail;
-    }
+    tier2_closure(g, t, bm, wl, &s_tail);
     // count the members of the type
     uint32_t c = 0;
     for (uint64_t w = tid; w < bm_words; w += kT2Block) {
@@ -220,6 +244,74 @@ __global__ __launch_bounds__(kT2Block) void lookup_tier2_kernel(LGraph g, const 
     }
 }
 
+// ---------------------------------------------------------------------- paged finish
+// The same closures with the ordered finish of paged_finish.hpp: request i reports count,
+// remaining and returned, and writes its page to the stride out + i * limit.
+__global__ __launch_bounds__(64) void lookup_page_tier1_kernel(LGraph g, const uint32_t *targets, const uint32_t *from,
+                                                               uint32_t n, uint32_t type, int force_tier2,
+                                                               paged::PageOut o, uint32_t *ovf_list,
+                                                               unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = targets[i];
+    if (t >= g.N) {  // NONE: the empty page; any other id outside the snapshot: INVALID
+        if (lane == 0) paged::page_invalid(o, i, t != KETOGPU_NODE_NONE);
+        return;
+    }
+    if (force_tier2 || !tier1_closure(g, t, lane, set, work)) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    paged::page_finish_wave(set, kSlotsLds, lane, i, from[i], o, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
+// Selection in id order first, then one scan that counts and clears: the slot is left all zero
+// for whichever kernel of the handle uses it next.
+__global__ __launch_bounds__(kT2Block) void lookup_page_tier2_kernel(LGraph g, const uint32_t *targets,
+                                                                     const uint32_t *from, uint32_t type,
+                                                                     paged::PageOut o, const uint32_t *ovf_list,
+                                                                     uint32_t first, uint32_t *bitmaps,
+                                                                     uint64_t bm_words, uint32_t *worklists) {
+    __shared__ unsigned int s_tail, s_cnt, s_rem;
+    __shared__ uint32_t s_wave[kT2Block / 64];
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const uint32_t t = targets[i];
+    uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
+    uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
+    const unsigned tid = threadIdx.x;
+    if (tid == 0) s_tail = 0, s_cnt = 0, s_rem = 0;
+    __syncthreads();
+    if (t >= g.N) return;  // (tier 1 lists valid targets only)
+    tier2_closure(g, t, bm, wl, &s_tail);
+    const uint32_t lo = from[i];
+    auto ok = [&](uint32_t u) { return type_ok(g, u, type); };
+    paged::page_select_block(bm, bm_words, lo, o.limit, o.out + (uint64_t)i * o.limit, s_wave, ok);
+    __syncthreads();  // the selection has read the bitmap
+    uint32_t c = 0, r = 0;
+    for (uint64_t w = tid; w < bm_words; w += kT2Block) {
+        uint32_t bits = bm[w];
+        if (!bits) continue;
+        bm[w] = 0;
+        while (bits) {
+            const uint32_t u = (uint32_t)(w << 5) + (uint32_t)__ffs(bits) - 1;
+            bits &= bits - 1;
+            const bool m = ok(u);
+            c += m;
+            r += m && u >= lo;
+        }
+    }
+    if (c) atomicAdd(&s_cnt, c);
+    if (r) atomicAdd(&s_rem, r);
+    __syncthreads();
+    if (tid == 0) {
+        o.count[i] = s_cnt;
+        o.remaining[i] = s_rem;
+        o.returned[i] = s_rem < o.limit ? s_rem : o.limit;
+    }
+}
+
 }  // namespace
 
 struct ketogpu_lookup {
@@ -235,6 +327,7 @@ struct ketogpu_lookup {
     DBuf<uint64_t> d_off;
     DBuf<uint32_t> d_col, d_type, d_targets, d_ovf, d_out, d_bm, d_wl;
     DBuf<unsigned long long> d_begin, d_count, d_ctr;  // d_ctr: cursor, truncated, overflow count
+    DBuf<uint32_t> d_from, d_ret;                       // paged calls: lower bounds, returned
     uint32_t slots = 0, slot_max = 0;  // tier 2: allocated slots; what budget and knob allow (0: not yet known)
     uint64_t bm_words = 0;
     ketogpu_lookup_stats st{};
@@ -287,22 +380,25 @@ struct ketogpu_lookup {
         st.slots = slots;
     }
 
+    // the rows of the snapshot's current version, uploaded again if a write moved it
+    void refresh() {
+        // (the link's lock is not held together with the snapshot's: a snapshot is not
+        // freed while a call on it runs, only before or after)
+        const Snapshot *sp;
+        {
+            std::lock_guard<std::mutex> lk(link->mu);
+            sp = link->snap;
+        }
+        if (!sp) throw Error(KETOGPU_EINVAL, "reverse lookup: the snapshot was freed");
+        std::shared_lock<std::shared_mutex> rd(sp->mu);
+        if (sp->version != version) upload(*sp);
+    }
+
     void run(const uint32_t *targets, size_t n, uint32_t type, uint32_t *out, uint64_t capacity, uint64_t *begin,
              uint64_t *count, uint64_t *needed) {
         const auto t0 = std::chrono::steady_clock::now();
         HIP_CHECK(hipSetDevice(device));
-        {
-            // (the link's lock is not held together with the snapshot's: a snapshot is not
-            // freed while a call on it runs, only before or after)
-            const Snapshot *sp;
-            {
-                std::lock_guard<std::mutex> lk(link->mu);
-                sp = link->snap;
-            }
-            if (!sp) throw Error(KETOGPU_EINVAL, "reverse lookup: the snapshot was freed");
-            std::shared_lock<std::shared_mutex> rd(sp->mu);
-            if (sp->version != version) upload(*sp);
-        }
+        refresh();
         *needed = 0;
         st.requests += n;
         if (n) {
@@ -346,11 +442,61 @@ struct ketogpu_lookup {
         st.last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 
+    // the paged call: run() with the ordered finish.  `from` may be null (all zero).
+    void run_page(const uint32_t *targets, const uint32_t *from, size_t n, uint32_t type, uint32_t limit, uint32_t *out,
+                  uint32_t *returned, uint64_t *count, uint64_t *remaining) {
+        const auto t0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipSetDevice(device));
+        refresh();
+        st.requests += n;
+        if (n) {
+            d_targets.need(n), d_from.need(n), d_ovf.need(n), d_ret.need(n), d_begin.need(n), d_count.need(n),
+                d_ctr.need(4), d_out.need(n * (size_t)limit);
+            HIP_CHECK(hipMemcpyAsync(d_targets.p, targets, n * 4, hipMemcpyHostToDevice, stream));
+            if (from)
+                HIP_CHECK(hipMemcpyAsync(d_from.p, from, n * 4, hipMemcpyHostToDevice, stream));
+            else
+                HIP_CHECK(hipMemsetAsync(d_from.p, 0, n * 4, stream));
+            HIP_CHECK(hipMemsetAsync(d_ctr.p, 0, 4 * sizeof(unsigned long long), stream));
+            paged::PageOut o{d_out.p, limit, d_ret.p, d_count.p, d_begin.p};  // (d_begin holds `remaining`)
+            unsigned int *ovf_count = (unsigned int *)(d_ctr.p + 2);
+            KLAUNCH(lookup_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_targets.p, d_from.p,
+                    (uint32_t)n, type, force_tier2 ? 1 : 0, o, d_ovf.p, ovf_count);
+            unsigned long long ctr[4];
+            HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            const uint32_t ovf = (uint32_t)(ctr[2] & 0xFFFFFFFFu);
+            if (ovf) {
+                need_slots(ovf);
+                for (uint32_t first = 0; first < ovf; first += slots) {
+                    const uint32_t k = std::min<uint32_t>(slots, ovf - first);
+                    KLAUNCH(lookup_page_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_targets.p, d_from.p,
+                            type, o, d_ovf.p, first, d_bm.p, bm_words, d_wl.p);
+                    st.tier2_rounds++;
+                }
+            }
+            HIP_CHECK(hipMemcpyAsync(returned, d_ret.p, n * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(count, d_count.p, n * 8, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(remaining, d_begin.p, n * 8, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(out, d_out.p, n * (size_t)limit * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            st.tier2_requests += ovf;
+            uint64_t unlisted = 0, produced = 0;
+            for (size_t i = 0; i < n; i++) {
+                unlisted += returned[i] == KETOGPU_PAGE_INVALID || targets[i] == NONE;
+                produced += returned[i] == KETOGPU_PAGE_INVALID ? 0 : returned[i];
+            }
+            st.tier1_requests += n - ovf - unlisted;
+            st.ids_produced += produced;
+        }
+        st.last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+
     ~ketogpu_lookup() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
         d_off.drop(), d_col.drop(), d_type.drop(), d_targets.drop(), d_ovf.drop(), d_out.drop(), d_bm.drop(), d_wl.drop();
-        d_begin.drop(), d_count.drop(), d_ctr.drop();
+        d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop();
     }
 };
 
@@ -411,6 +557,26 @@ int ketogpu_lookup_ids(ketogpu_lookup *l, const uint32_t *targets, size_t n, uin
     return guarded([&] {
         std::lock_guard<std::mutex> lk(l->mu);
         l->run(targets, n, type, out, capacity, begin, count, needed);
+    });
+}
+
+int ketogpu_lookup_page(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *from, size_t n, uint32_t type,
+                        uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count, uint64_t *remaining) {
+    if (!l || (n && (!targets || !out || !returned || !count || !remaining))) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    if (!limit || limit > KETOGPU_PAGE_LIMIT_MAX) {
+        set_last_error("reverse lookup: a page limit outside [1, KETOGPU_PAGE_LIMIT_MAX]");
+        return KETOGPU_EINVAL;
+    }
+    if (n >= (1ull << 31)) {
+        set_last_error("reverse lookup: more than 2^31 - 1 targets in one call");
+        return KETOGPU_EINVAL;
+    }
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(l->mu);
+        l->run_page(targets, from, n, type, limit, out, returned, count, remaining);
     });
 }
 

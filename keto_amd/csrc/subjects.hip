@@ -24,6 +24,11 @@
 // `out` with one device-scope atomicAdd on a cursor, and write the list with plain vector
 // stores if it fits below `capacity` (else begin = TRUNCATED; the count is exact either way).
 //
+// The paged call (ketogpu_subjects_page) runs the same two closures (tier1_closure, tier2_closure: one
+// implementation each, called by the full-list and the paged kernel) and ends with the ordered
+// finish of paged_finish.hpp instead: the `limit` smallest members >= from[i] to the stride
+// out + i * limit, ascending, with the exact count and what remains; no cursor, no truncation.
+//
 // Every index is validated before it is used: roots against N, and against Nx before fwd_off
 // is touched; row entries against N before the class array or a bitmap is.
 #include <hip/hip_runtime.h>
@@ -32,6 +37,7 @@
 #include <cstdlib>
 
 #include "hip_host.hpp"
+#include "paged_finish.hpp"
 #include "subjects.hpp"
 
 using namespace ketogpu;
@@ -42,6 +48,7 @@ constexpr uint32_t kSetCap = 1024;           // tier 1: nodes a set may hold (ke
 constexpr uint32_t kSlotsLds = 2 * kSetCap;  // hash slots: a load of at most (kSetCap + 64) / kSlotsLds
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 constexpr unsigned kT2Block = 256;
+static_assert(kT2Block == paged::kBlock, "the paged selection assumes tier 2's workgroup");
 constexpr uint32_t kListCapDefault = 65536;  // tier 2: 256 KiB of seen list per slot
 
 struct SGraph {
@@ -72,25 +79,10 @@ __device__ inline uint32_t slot_of(uint32_t u) { return (u * 0x9E3779B1u) >> 21;
 static_assert(kSlotsLds == 1u << 11, "slot_of yields 11 bits");
 
 // ---------------------------------------------------------------------- tier 1
-__global__ __launch_bounds__(64) void subjects_tier1_kernel(SGraph g, const uint32_t *roots, uint32_t n, uint32_t cls,
-                                                            int force_tier2, SOut o, uint32_t *ovf_list,
-                                                            unsigned int *ovf_count) {
-    __shared__ uint32_t set[kSlotsLds];
-    __shared__ uint32_t work[kSetCap + 64];
-    const uint32_t i = blockIdx.x, lane = threadIdx.x;
-    if (i >= n) return;
-    const uint32_t r = roots[i];
-    if (r >= g.Nx) {  // NONE and the never-expanded nodes: the empty list; an id outside the snapshot: INVALID
-        if (lane == 0) {
-            o.begin[i] = (r < g.N || r == KETOGPU_NODE_NONE) ? 0ull : KETOGPU_LOOKUP_INVALID;
-            o.count[i] = 0;
-        }
-        return;
-    }
-    if (force_tier2) {
-        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
-        return;
-    }
+// tier 1's closure, by one wave: F(r) into `set` (all kSlotsLds slots are initialised here), its
+// interior members through `work`.  False when the set passed kSetCap: the request overflows.
+__device__ __forceinline__ bool tier1_closure(const SGraph &g, uint32_t r, uint32_t lane, uint32_t *set,
+                                              uint32_t *work) {
     for (uint32_t s = lane; s < kSlotsLds; s += 64) set[s] = kEmpty;
     __syncthreads();
     uint32_t size = 0, head = 0, tail = 0;  // wave-uniform
@@ -125,6 +117,29 @@ __global__ __launch_bounds__(64) void subjects_tier1_kernel(SGraph g, const uint
         if (over || head == tail) break;
         v = work[head++];
     }
+    return !over;
+}
+
+__global__ __launch_bounds__(64) void subjects_tier1_kernel(SGraph g, const uint32_t *roots, uint32_t n, uint32_t cls,
+                                                            int force_tier2, SOut o, uint32_t *ovf_list,
+                                                            unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = roots[i];
+    if (r >= g.Nx) {  // NONE and the never-expanded nodes: the empty list; an id outside the snapshot: INVALID
+        if (lane == 0) {
+            o.begin[i] = (r < g.N || r == KETOGPU_NODE_NONE) ? 0ull : KETOGPU_LOOKUP_INVALID;
+            o.count[i] = 0;
+        }
+        return;
+    }
+    if (force_tier2) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    const bool over = !tier1_closure(g, r, lane, set, work);
     if (over) {
         if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
         return;
@@ -152,6 +167,40 @@ __global__ __launch_bounds__(64) void subjects_tier1_kernel(SGraph g, const uint
 }
 
 // ---------------------------------------------------------------------- tier 2
+// tier 2's closure, by the whole workgroup: F(r) into the slot's bitmap `bm` (all zero on entry),
+// its interior members through the worklist `wl`; every first visit is counted in *s_seen and,
+// while there is room, appended to `seen`.  *s_tail and *s_seen are LDS counters, zero on entry
+// and published by a barrier.  Ends behind a barrier: every thread sees the whole state.
+__device__ __forceinline__ void tier2_closure(const SGraph &g, uint32_t r, uint32_t *bm, uint32_t *wl, uint32_t *seen,
+                                              uint32_t list_cap, unsigned int *s_tail, unsigned int *s_seen) {
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = kT2Block / 64;
+    auto visit = [&](uint32_t u) {
+        if (u >= g.N) return;
+        const uint32_t bit = 1u << (u & 31);
+        if (atomicOr(&bm[u >> 5], bit) & bit) return;
+        const uint32_t k = atomicAdd(s_seen, 1u);  // every first visit is counted
+        if (k < list_cap) seen[k] = u;
+        if (u < g.Ni) wl[atomicAdd(s_tail, 1u)] = u;  // each interior node enters once: <= Ni entries
+    };
+    {  // the root's own row, by the whole workgroup
+        const uint64_t b = g.fwd_off[r], e = g.fwd_off[r + 1];
+        for (uint64_t j = b + tid; j < e; j += kT2Block) visit(g.fwd_col[j]);
+    }
+    __syncthreads();
+    uint32_t lb = 0, le = *s_tail;
+    while (lb < le) {  // one level: a wave per row
+        __syncthreads();  // everyone has read s_tail before it moves
+        for (uint32_t k = lb + wave; k < le; k += nwaves) {
+            const uint32_t v = wl[k];
+            const uint64_t b = g.fwd_off[v], e = g.fwd_off[v + 1];
+            for (uint64_t j = b + lane; j < e; j += 64) visit(g.fwd_col[j]);
+        }
+        __syncthreads();
+        lb = le;
+        le = *s_tail;
+    }
+}
+
 // Block s of round r serves overflow request ovf_list[first + s] with slot s's state.  The
 // bitmap is all zero on entry and is cleared again on the way out, by either finish.
 __global__ __launch_bounds__(kT2Block) void subjects_tier2_kernel(SGraph g, const uint32_t *roots, uint32_t cls, SOut o,
@@ -166,35 +215,11 @@ __global__ __launch_bounds__(kT2Block) void subjects_tier2_kernel(SGraph g, cons
     uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
     uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
     uint32_t *seen = seen_lists + (uint64_t)blockIdx.x * list_cap;
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = kT2Block / 64;
+    const unsigned tid = threadIdx.x, lane = tid & 63;
     if (tid == 0) s_tail = 0, s_seen = 0, s_cnt = 0, s_pos = 0;
     __syncthreads();
     if (r >= g.Nx) return;  // (tier 1 lists expandable roots only)
-    auto visit = [&](uint32_t u) {
-        if (u >= g.N) return;
-        const uint32_t bit = 1u << (u & 31);
-        if (atomicOr(&bm[u >> 5], bit) & bit) return;
-        const uint32_t k = atomicAdd(&s_seen, 1u);  // every first visit is counted
-        if (k < list_cap) seen[k] = u;
-        if (u < g.Ni) wl[atomicAdd(&s_tail, 1u)] = u;  // each interior node enters once: <= Ni entries
-    };
-    {  // the root's own row, by the whole workgroup
-        const uint64_t b = g.fwd_off[r], e = g.fwd_off[r + 1];
-        for (uint64_t j = b + tid; j < e; j += kT2Block) visit(g.fwd_col[j]);
-    }
-    __syncthreads();
-    uint32_t lb = 0, le = s_tail;
-    while (lb < le) {  // one level: a wave per row
-        __syncthreads();  // everyone has read s_tail before it moves
-        for (uint32_t k = lb + wave; k < le; k += nwaves) {
-            const uint32_t v = wl[k];
-            const uint64_t b = g.fwd_off[v], e = g.fwd_off[v + 1];
-            for (uint64_t j = b + lane; j < e; j += 64) visit(g.fwd_col[j]);
-        }
-        __syncthreads();
-        lb = le;
-        le = s_tail;
-    }
+    tier2_closure(g, r, bm, wl, seen, list_cap, &s_tail, &s_seen);
     const uint32_t total = s_seen;
     const bool by_list = list_cap && total <= list_cap;  // the seen list holds the whole closure
     // count the members of the class
@@ -259,6 +284,92 @@ __global__ __launch_bounds__(kT2Block) void subjects_tier2_kernel(SGraph g, cons
     }
 }
 
+// ---------------------------------------------------------------------- paged finish
+// The same closures with the ordered finish of paged_finish.hpp: request i reports count,
+// remaining and returned, and writes its page to the stride out + i * limit.
+__global__ __launch_bounds__(64) void subjects_page_tier1_kernel(SGraph g, const uint32_t *roots, const uint32_t *from,
+                                                                 uint32_t n, uint32_t cls, int force_tier2,
+                                                                 paged::PageOut o, uint32_t *ovf_list,
+                                                                 unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = roots[i];
+    if (r >= g.Nx) {  // NONE and the never-expanded nodes: the empty page; an id outside the snapshot: INVALID
+        if (lane == 0) paged::page_invalid(o, i, !(r < g.N || r == KETOGPU_NODE_NONE));
+        return;
+    }
+    if (force_tier2 || !tier1_closure(g, r, lane, set, work)) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    paged::page_finish_wave(set, kSlotsLds, lane, i, from[i], o, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
+// Selection in id order first; then the members are counted and the bitmap cleared, by the
+// seen list if it holds the whole closure and by one scan otherwise: the slot is left all zero
+// for whichever kernel of the handle uses it next.
+__global__ __launch_bounds__(kT2Block) void subjects_page_tier2_kernel(SGraph g, const uint32_t *roots,
+                                                                       const uint32_t *from, uint32_t cls,
+                                                                       paged::PageOut o, unsigned long long *list_finishes,
+                                                                       unsigned long long *scan_finishes,
+                                                                       const uint32_t *ovf_list, uint32_t first,
+                                                                       uint32_t *bitmaps, uint64_t bm_words,
+                                                                       uint32_t *worklists, uint32_t *seen_lists,
+                                                                       uint32_t list_cap) {
+    __shared__ unsigned int s_tail, s_seen, s_cnt, s_rem;
+    __shared__ uint32_t s_wave[kT2Block / 64];
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const uint32_t r = roots[i];
+    uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
+    uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
+    uint32_t *seen = seen_lists + (uint64_t)blockIdx.x * list_cap;
+    const unsigned tid = threadIdx.x;
+    if (tid == 0) s_tail = 0, s_seen = 0, s_cnt = 0, s_rem = 0;
+    __syncthreads();
+    if (r >= g.Nx) return;  // (tier 1 lists expandable roots only)
+    tier2_closure(g, r, bm, wl, seen, list_cap, &s_tail, &s_seen);
+    const uint32_t total = s_seen;
+    const bool by_list = list_cap && total <= list_cap;  // the seen list holds the whole closure
+    const uint32_t lo = from[i];
+    auto ok = [&](uint32_t u) { return class_ok(g, u, cls); };
+    paged::page_select_block(bm, bm_words, lo, o.limit, o.out + (uint64_t)i * o.limit, s_wave, ok);
+    __syncthreads();  // the selection has read the bitmap
+    uint32_t c = 0, q = 0;
+    if (by_list) {
+        for (uint32_t k = tid; k < total; k += kT2Block) {
+            const uint32_t u = seen[k];
+            const bool m = ok(u);
+            c += m;
+            q += m && u >= lo;
+            bm[u >> 5] = 0;  // every set bit of the word is some member's: all of them store the same zero
+        }
+    } else {
+        for (uint64_t w = tid; w < bm_words; w += kT2Block) {
+            uint32_t bits = bm[w];
+            if (!bits) continue;
+            bm[w] = 0;
+            while (bits) {
+                const uint32_t u = (uint32_t)(w << 5) + (uint32_t)__ffs(bits) - 1;
+                bits &= bits - 1;
+                const bool m = ok(u);
+                c += m;
+                q += m && u >= lo;
+            }
+        }
+    }
+    if (c) atomicAdd(&s_cnt, c);
+    if (q) atomicAdd(&s_rem, q);
+    __syncthreads();
+    if (tid == 0) {
+        o.count[i] = s_cnt;
+        o.remaining[i] = s_rem;
+        o.returned[i] = s_rem < o.limit ? s_rem : o.limit;
+        atomicAdd(by_list ? list_finishes : scan_finishes, 1ull);
+    }
+}
+
 }  // namespace
 
 struct ketogpu_subjects {
@@ -275,6 +386,7 @@ struct ketogpu_subjects {
     DBuf<uint64_t> d_off;
     DBuf<uint32_t> d_col, d_class, d_roots, d_ovf, d_out, d_bm, d_wl, d_seen;
     DBuf<unsigned long long> d_begin, d_count, d_ctr;  // d_ctr: cursor, truncated, overflow count, list / scan finishes
+    DBuf<uint32_t> d_from, d_ret;      // paged calls: lower bounds, returned
     uint32_t slots = 0, slot_max = 0;  // tier 2: allocated slots; what budget and knob allow (0: not yet known)
     uint64_t bm_words = 0;
     std::vector<uint64_t> h_off;  // upload staging
@@ -339,22 +451,25 @@ struct ketogpu_subjects {
         st.slots = slots;
     }
 
+    // the rows of the snapshot's current version, uploaded again if a write moved it
+    void refresh() {
+        // (the link's lock is not held together with the snapshot's: a snapshot is not
+        // freed while a call on it runs, only before or after)
+        const Snapshot *sp;
+        {
+            std::lock_guard<std::mutex> lk(link->mu);
+            sp = link->snap;
+        }
+        if (!sp) throw Error(KETOGPU_EINVAL, "subject listing: the snapshot was freed");
+        std::shared_lock<std::shared_mutex> rd(sp->mu);
+        if (sp->version != version) upload(*sp);
+    }
+
     void run(const uint32_t *roots, size_t n, uint32_t cls, uint32_t *out, uint64_t capacity, uint64_t *begin,
              uint64_t *count, uint64_t *needed) {
         const auto t0 = std::chrono::steady_clock::now();
         HIP_CHECK(hipSetDevice(device));
-        {
-            // (the link's lock is not held together with the snapshot's: a snapshot is not
-            // freed while a call on it runs, only before or after)
-            const Snapshot *sp;
-            {
-                std::lock_guard<std::mutex> lk(link->mu);
-                sp = link->snap;
-            }
-            if (!sp) throw Error(KETOGPU_EINVAL, "subject listing: the snapshot was freed");
-            std::shared_lock<std::shared_mutex> rd(sp->mu);
-            if (sp->version != version) upload(*sp);
-        }
+        refresh();
         *needed = 0;
         st.requests += n;
         if (n) {
@@ -400,11 +515,64 @@ struct ketogpu_subjects {
         st.last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 
+    // the paged call: run() with the ordered finish.  `from` may be null (all zero).
+    void run_page(const uint32_t *roots, const uint32_t *from, size_t n, uint32_t cls, uint32_t limit, uint32_t *out,
+                  uint32_t *returned, uint64_t *count, uint64_t *remaining) {
+        const auto t0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipSetDevice(device));
+        refresh();
+        st.requests += n;
+        if (n) {
+            d_roots.need(n), d_from.need(n), d_ovf.need(n), d_ret.need(n), d_begin.need(n), d_count.need(n),
+                d_ctr.need(8), d_out.need(n * (size_t)limit);
+            HIP_CHECK(hipMemcpyAsync(d_roots.p, roots, n * 4, hipMemcpyHostToDevice, stream));
+            if (from)
+                HIP_CHECK(hipMemcpyAsync(d_from.p, from, n * 4, hipMemcpyHostToDevice, stream));
+            else
+                HIP_CHECK(hipMemsetAsync(d_from.p, 0, n * 4, stream));
+            HIP_CHECK(hipMemsetAsync(d_ctr.p, 0, 8 * sizeof(unsigned long long), stream));
+            paged::PageOut o{d_out.p, limit, d_ret.p, d_count.p, d_begin.p};  // (d_begin holds `remaining`)
+            unsigned int *ovf_count = (unsigned int *)(d_ctr.p + 2);
+            KLAUNCH(subjects_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_roots.p, d_from.p,
+                    (uint32_t)n, cls, force_tier2 ? 1 : 0, o, d_ovf.p, ovf_count);
+            unsigned long long ctr[8];
+            HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            const uint32_t ovf = (uint32_t)(ctr[2] & 0xFFFFFFFFu);
+            if (ovf) {
+                need_slots(ovf);
+                for (uint32_t first = 0; first < ovf; first += slots) {
+                    const uint32_t k = std::min<uint32_t>(slots, ovf - first);
+                    KLAUNCH(subjects_page_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_roots.p, d_from.p, cls,
+                            o, d_ctr.p + 3, d_ctr.p + 4, d_ovf.p, first, d_bm.p, bm_words, d_wl.p, d_seen.p, list_cap);
+                    st.tier2_rounds++;
+                }
+                HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
+            }
+            HIP_CHECK(hipMemcpyAsync(returned, d_ret.p, n * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(count, d_count.p, n * 8, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(remaining, d_begin.p, n * 8, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(out, d_out.p, n * (size_t)limit * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            st.tier2_requests += ovf;
+            uint64_t unlisted = 0, produced = 0;  // INVALID and NONE roots belong to neither tier
+            for (size_t i = 0; i < n; i++) {
+                unlisted += returned[i] == KETOGPU_PAGE_INVALID || roots[i] == NONE;
+                produced += returned[i] == KETOGPU_PAGE_INVALID ? 0 : returned[i];
+            }
+            st.tier1_requests += n - ovf - unlisted;
+            st.list_finishes += ctr[3];
+            st.scan_finishes += ctr[4];
+            st.ids_produced += produced;
+        }
+        st.last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+
     ~ketogpu_subjects() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
         d_off.drop(), d_col.drop(), d_class.drop(), d_roots.drop(), d_ovf.drop(), d_out.drop(), d_bm.drop(), d_wl.drop();
-        d_seen.drop(), d_begin.drop(), d_count.drop(), d_ctr.drop();
+        d_seen.drop(), d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop();
     }
 };
 
@@ -468,6 +636,26 @@ int ketogpu_subjects_ids(ketogpu_subjects *h, const uint32_t *roots, size_t n, u
     return guarded([&] {
         std::lock_guard<std::mutex> lk(h->mu);
         h->run(roots, n, cls, out, capacity, begin, count, needed);
+    });
+}
+
+int ketogpu_subjects_page(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *from, size_t n, uint32_t cls,
+                          uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count, uint64_t *remaining) {
+    if (!h || (n && (!roots || !out || !returned || !count || !remaining))) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    if (!limit || limit > KETOGPU_PAGE_LIMIT_MAX) {
+        set_last_error("subject listing: a page limit outside [1, KETOGPU_PAGE_LIMIT_MAX]");
+        return KETOGPU_EINVAL;
+    }
+    if (n >= (1ull << 31)) {
+        set_last_error("subject listing: more than 2^31 - 1 roots in one call");
+        return KETOGPU_EINVAL;
+    }
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->run_page(roots, from, n, cls, limit, out, returned, count, remaining);
     });
 }
 

@@ -8,6 +8,8 @@ caller gets the reference's responses from the new engines:
     POST /check    internal/check/handler.go:128-146  same; a JSON decode error is 400
     GET  /expand   internal/expand/handler.go:78-92   200 tree | null, 400 bad max-depth, 404 unknown namespace
     POST /check/batch  (new, SURVEY.md 8(f) row 2)    200 {"results": [{"allowed": bool} | {"error": ...}]}
+    GET  /list/objects   (new, DESIGN.md "Sorted, paged lists")  200 {"objects": [...], "next_page_token", "total"}
+    GET  /list/subjects  (new, same section)                     200 {"subjects": [...], "next_page_token", "total"}
 
 URL parsing restates RelationQuery.FromURLQuery (internal/relationtuple/definitions.go:
 458-493): a bare "subject" key, both subject forms, or an incomplete subject_set are 400;
@@ -25,7 +27,7 @@ routes with http.server (a demo harness; the production server is Keto's own).
 import json
 from urllib.parse import parse_qs
 
-from . import check, expand
+from . import _lib, check, expand
 from .relationtuple import InternalRelationTuple, NilSubject, SubjectID, SubjectSet
 
 SUBJECT_ID = "subject_id"
@@ -160,11 +162,16 @@ def go_parse_int(s):
 
 
 class Handler:
-    """(status, JSON body) for each route; engines are check.Engine and expand.Engine"""
+    """(status, JSON body) for each route; engines are check.Engine and expand.Engine.  `lookup`
+    and `subjects` are any objects with list_objects_page / list_subjects_page (lookup.Lookup /
+    lookup.Subjects on the device, lookup.HostLookup / lookup.HostSubjects without one); without
+    them the list routes answer 404."""
 
-    def __init__(self, check_engine: check.Engine, expand_engine: expand.Engine):
+    def __init__(self, check_engine: check.Engine, expand_engine: expand.Engine, lookup=None, subjects=None):
         self.check = check_engine
         self.expand = expand_engine
+        self.lookup = lookup
+        self.subjects = subjects
 
     @staticmethod
     def _error(code, reason):
@@ -236,6 +243,60 @@ class Handler:
         return 200, {"results": results}
 
 
+    # ---- paged lists (page_size / page_token in, next_page_token out: Keto's list convention,
+    # internal/x/pagination.go; the order is by node id)
+    def _page_args(self, q):
+        """-> (page_size, page_token); page_size defaults to 100 and is parsed as Go parses an int"""
+        raw = _get(q, "page_size")
+        size = 100
+        if raw is not None and raw != "":
+            try:
+                size = go_parse_int(raw)
+            except ValueError as e:
+                raise BadRequest(f"strconv.ParseInt: parsing {json.dumps(raw)}: {e}")
+        if not 1 <= size <= _lib.PAGE_LIMIT_MAX:
+            raise BadRequest(f"page_size {size} is outside [1, {_lib.PAGE_LIMIT_MAX}]")
+        return size, _get(q, "page_token") or ""
+
+    def _list(self, backend, query, call):
+        if backend is None:
+            return self._error(404, "this server has no list handle")
+        q = parse_qs(query, keep_blank_values=True) if isinstance(query, str) else query
+        try:
+            size, token = self._page_args(q)
+            return 200, call(q, size, token)
+        except BadRequest as e:
+            return self._error(400, str(e))
+        except _lib.KetoError as e:  # a malformed token, a wildcard root without a node
+            if e.code != _lib.EINVAL:
+                raise
+            return self._error(400, str(e))
+
+    def get_list_objects(self, query):
+        """namespace, relation, subject_id | subject_set.*, page_size, page_token -> the objects o
+        with Check(namespace:o#relation@subject)"""
+        def call(q, size, token):
+            t = tuple_from_url(q)  # the subject is required
+            items, nxt, total = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size, token)
+            return {"objects": items, "next_page_token": nxt, "total": total}
+        return self._list(self.lookup, query, call)
+
+    def get_list_subjects(self, query):
+        """namespace, object, relation, kind (ids | any | ns#relation), page_size, page_token -> the
+        subjects s with Check(namespace:object#relation@s), in the JSON form check requests use"""
+        def call(q, size, token):
+            kind = _get(q, "kind") or "ids"
+            if kind not in ("ids", "any"):
+                ns, sep, rel = kind.partition("#")
+                if not sep:
+                    raise BadRequest(f'kind {kind!r}: expected "ids", "any" or "namespace#relation"')
+                kind = (ns, rel)
+            items, nxt, total = self.subjects.list_subjects_page(
+                _get(q, "namespace") or "", _get(q, "object") or "", _get(q, "relation") or "", kind, size, token)
+            return {"subjects": [s.to_dict() for s in items], "next_page_token": nxt, "total": total}
+        return self._list(self.subjects, query, call)
+
+
 def serve(handler: Handler, port: int):  # pragma: no cover - demo harness
     from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
     from urllib.parse import urlsplit
@@ -255,6 +316,10 @@ def serve(handler: Handler, port: int):  # pragma: no cover - demo harness
                 self._send(*handler.get_check(u.query))
             elif u.path == "/expand":
                 self._send(*handler.get_expand(u.query))
+            elif u.path == "/list/objects":
+                self._send(*handler.get_list_objects(u.query))
+            elif u.path == "/list/subjects":
+                self._send(*handler.get_list_subjects(u.query))
             else:
                 self._send(404, {"error": {"code": 404, "status": "Not Found"}})
 
@@ -283,7 +348,13 @@ def main():  # pragma: no cover - demo harness
     ns = [(x.split(":")[0], int(x.split(":")[1])) for x in a.namespaces.split(",")]
     tuples = [InternalRelationTuple.FromString(line.strip()) for line in open(a.tuples) if line.strip()]
     snap = Snapshot.from_tuples(ns, tuples)
-    serve(Handler(check.Engine(snap), expand.Engine(snap)), a.port)
+    from . import lookup
+    try:
+        lists = (lookup.Lookup(snap), lookup.Subjects(snap))
+    except _lib.KetoError as e:  # shared Subject.String() keys (R4): the list routes answer 404
+        print(f"no list routes: {e}")
+        lists = (None, None)
+    serve(Handler(check.Engine(snap), expand.Engine(snap), *lists), a.port)
 
 
 if __name__ == "__main__":

@@ -11,6 +11,12 @@ subjects(r, C) is the set of nodes t of class C with SubjectIsAllowed(r, t): the
 closure F(r) over the rows the check engine sees (DESIGN.md "Subject listing").
 `host_subjects` walks the rows on the CPU; `Subjects` is the device handle
 (keto_amd/csrc/subjects.hip).
+
+Both questions also come sorted and paged (ketogpu_lookup_page / ketogpu_subjects_page,
+DESIGN.md "Sorted, paged lists"): `*_page_raw` on ids, `list_*_page` on names with Keto's
+page_size / page_token convention.  The order is by node id.  `HostLookup` / `HostSubjects` are
+the CPU twins with the same methods: the yardstick of the device calls, and a backend for the
+HTTP routes where there is no GPU.
 """
 import ctypes as C
 
@@ -23,6 +29,127 @@ from .relationtuple import SubjectID, SubjectSet
 TYPE_ANY, TYPE_NONE = L.TYPE_ANY, L.TYPE_NONE
 TRUNCATED, INVALID = L.LOOKUP_TRUNCATED, L.LOOKUP_INVALID
 CLASS_SUBJECT_ID, CLASS_UNTYPED_SET = L.CLASS_SUBJECT_ID, L.CLASS_UNTYPED_SET
+PAGE_LIMIT_MAX, PAGE_INVALID = L.PAGE_LIMIT_MAX, L.PAGE_INVALID
+
+
+# ---- pages: tokens and sizes, shared by the device handles and their CPU twins
+def parse_page_token(token):
+    """"" (the first page) -> 0; otherwise the decimal string of the next lower bound: at most
+    10 digits and <= 0xFFFFFFFF, anything else raises KetoError(EINVAL)"""
+    if token == "":
+        return 0
+    if not isinstance(token, str) or len(token) > 10 or not (token.isascii() and token.isdigit()) \
+            or int(token) > 0xFFFFFFFF:
+        raise L.KetoError(L.EINVAL, f"malformed page token {token!r}")
+    return int(token)
+
+
+def check_page_size(page_size):
+    if isinstance(page_size, bool) or not isinstance(page_size, (int, np.integer)) \
+            or not 1 <= page_size <= PAGE_LIMIT_MAX:
+        raise L.KetoError(L.EINVAL, f"page size {page_size!r} is outside [1, {PAGE_LIMIT_MAX}]")
+    return int(page_size)
+
+
+def next_page_token(ids, returned, remaining):
+    """"" exactly when nothing remains after this page, else the id after the page's last"""
+    return "" if int(remaining) == int(returned) else str(int(ids[int(returned) - 1]) + 1)
+
+
+def _page_of(ids, lo, limit):
+    """one request of a CPU twin: the page of an ascending list -> (ids, count, remaining)"""
+    k = int(np.searchsorted(ids, lo, side="left"))
+    return ids[k:k + limit], len(ids), len(ids) - k
+
+
+def _host_pages(lists, invalid, from_ids, limit):
+    """(out[n, limit], returned, count, remaining) as the device calls return them"""
+    limit = check_page_size(limit)
+    n = len(lists)
+    lo = np.zeros(n, dtype=np.uint32) if from_ids is None else np.ascontiguousarray(from_ids, dtype=np.uint32)
+    if len(lo) != n:
+        raise L.KetoError(L.EINVAL, "one lower bound per request")
+    out = np.zeros((n, limit), dtype=np.uint32)
+    returned = np.zeros(n, dtype=np.uint32)
+    count, remaining = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    for i, ids in enumerate(lists):
+        if invalid[i]:
+            returned[i] = PAGE_INVALID
+            continue
+        page, count[i], remaining[i] = _page_of(ids, lo[i], limit)
+        out[i, :len(page)] = page
+        returned[i] = len(page)
+    return out, returned, count, remaining
+
+
+def _page_args(ids, from_ids, limit):
+    """the arrays of one ketogpu_*_page call (the library itself judges `limit`)"""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    n = len(ids)
+    lo = None if from_ids is None else np.ascontiguousarray(from_ids, dtype=np.uint32)
+    if lo is not None and len(lo) != n:
+        raise L.KetoError(L.EINVAL, "one lower bound per request")
+    limit = int(limit)
+    width = limit if 1 <= limit <= PAGE_LIMIT_MAX else 1
+    out = np.empty((max(n, 1), width), dtype=np.uint32)
+    returned = np.empty(max(n, 1), dtype=np.uint32)
+    count = np.empty(max(n, 1), dtype=np.uint64)
+    remaining = np.empty(max(n, 1), dtype=np.uint64)
+    return ids, lo, n, limit, out, returned, count, remaining
+
+
+class _ObjectPages:
+    """list_objects_page over self.lookup_page_raw and self.snapshot"""
+
+    def list_objects_page_batch(self, namespace, relation, requests, page_size=100):
+        """requests: (subject, page_token) pairs, one device call for all of them -> per
+        request (object names in node-id order, next_page_token, total)"""
+        page_size = check_page_size(page_size)
+        requests = list(requests)
+        lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
+        ty = self.snapshot.type_id(namespace, relation)
+        targets = resolve_subjects(self.snapshot, [s for s, _ in requests])
+        if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
+            return [([], "", 0) for _ in requests]
+        out, returned, count, remaining = self.lookup_page_raw(targets, lo, ty, page_size)
+        res = []
+        for i in range(len(requests)):
+            k = int(returned[i])
+            names = [self.snapshot.node_info(int(v))["id"] for v in out[i, :k]]
+            res.append((names, next_page_token(out[i], k, remaining[i]), int(count[i])))
+        return res
+
+    def list_objects_page(self, namespace, relation, subject, page_size=100, page_token=""):
+        """-> (items, next_page_token, total): at most page_size object names o with
+        Check(namespace:o#relation@subject), in node-id order from the token on"""
+        return self.list_objects_page_batch(namespace, relation, [(subject, page_token)], page_size)[0]
+
+
+class _SubjectPages:
+    """list_subjects_page over self.subject_page_raw and self.snapshot"""
+
+    def list_subjects_page_batch(self, requests, kind="ids", page_size=100):
+        """requests: ((namespace, object, relation), page_token) pairs, one device call for all
+        of them -> per request (SubjectID / SubjectSet in node-id order, next_page_token, total)"""
+        page_size = check_page_size(page_size)
+        requests = list(requests)
+        lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
+        cls = _class_of_kind(self.snapshot, kind)
+        roots = resolve_roots(self.snapshot, [tuple(r) for r, _ in requests])
+        if cls == TYPE_NONE:
+            return [([], "", 0) for _ in requests]
+        out, returned, count, remaining = self.subject_page_raw(roots, lo, cls, page_size)
+        res = []
+        for i in range(len(requests)):
+            k = int(returned[i])
+            subs = [self.snapshot.describe(int(v)) for v in out[i, :k]]
+            res.append((subs, next_page_token(out[i], k, remaining[i]), int(count[i])))
+        return res
+
+    def list_subjects_page(self, namespace, object, relation, kind="ids", page_size=100, page_token=""):
+        """-> (items, next_page_token, total): at most page_size subjects s with
+        Check(namespace:object#relation@s), in node-id order from the token on"""
+        return self.list_subjects_page_batch([((namespace, object, relation), page_token)], kind, page_size)[0]
 
 
 def host_lookup(snapshot, target, type_id=TYPE_ANY):
@@ -50,7 +177,7 @@ def resolve_subjects(snapshot, subjects):
     return targets.copy()
 
 
-class Lookup:
+class Lookup(_ObjectPages):
     """device handle over a snapshot's reverse rows.  A write to a writable snapshot is seen by
     the next call (the rows are uploaded again when the snapshot's version has moved)."""
 
@@ -114,6 +241,16 @@ class Lookup:
             idx = idx[~done]
         return res
 
+    def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100):
+        """one ketogpu_lookup_page call -> (out[n, limit], returned, count, remaining): row i
+        holds the returned[i] smallest members >= from_ids[i], ascending; count[i] the whole
+        list's size; returned[i] PAGE_INVALID for an id outside the snapshot"""
+        targets, lo, n, limit, out, returned, count, remaining = _page_args(targets, from_ids, limit)
+        L.check(self.L.ketogpu_lookup_page(self.h, targets.ctypes.data, None if lo is None else lo.ctypes.data, n,
+                                           int(type_id), limit, out.ctypes.data, returned.ctypes.data,
+                                           count.ctypes.data, remaining.ctypes.data))
+        return out[:n], returned[:n], count[:n], remaining[:n]
+
     # ---- names
     def _objects(self, ids):
         return sorted(self.snapshot.node_info(int(v))["id"] for v in ids)
@@ -137,6 +274,20 @@ def host_list_objects(snapshot, namespace, relation, subject):
     if ty == TYPE_NONE or t == L.NODE_NONE:
         return []
     return sorted(snapshot.node_info(int(v))["id"] for v in host_lookup(snapshot, t, ty))
+
+
+class HostLookup(_ObjectPages):
+    """Lookup's paged calls on the CPU: host_lookup's ascending lists, sliced"""
+
+    def __init__(self, snapshot):
+        self.snapshot = snapshot
+
+    def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100):
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        n_nodes = self.snapshot.stats()["num_nodes"]
+        invalid = [t >= n_nodes and t != L.NODE_NONE for t in targets]
+        lists = [None if bad else host_lookup(self.snapshot, int(t), type_id) for t, bad in zip(targets, invalid)]
+        return _host_pages(lists, invalid, from_ids, limit)
 
 
 def host_subjects(snapshot, root, cls=TYPE_ANY):
@@ -187,7 +338,7 @@ def _subjects_of(snapshot, ids):
     return users + sets
 
 
-class Subjects:
+class Subjects(_SubjectPages):
     """device handle over a snapshot's forward rows.  A write to a writable snapshot is seen by
     the next call (the rows are uploaded again when the snapshot's version has moved)."""
 
@@ -251,6 +402,16 @@ class Subjects:
             idx = idx[~done]
         return res
 
+    def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100):
+        """one ketogpu_subjects_page call -> (out[n, limit], returned, count, remaining): row i
+        holds the returned[i] smallest members >= from_ids[i], ascending; count[i] the whole
+        list's size; returned[i] PAGE_INVALID for an id outside the snapshot"""
+        roots, lo, n, limit, out, returned, count, remaining = _page_args(roots, from_ids, limit)
+        L.check(self.L.ketogpu_subjects_page(self.h, roots.ctypes.data, None if lo is None else lo.ctypes.data, n,
+                                             int(cls), limit, out.ctypes.data, returned.ctypes.data,
+                                             count.ctypes.data, remaining.ctypes.data))
+        return out[:n], returned[:n], count[:n], remaining[:n]
+
     # ---- names
     def list_subjects_batch(self, roots, kind="ids"):
         """per (namespace, object, relation) root: the subjects s with Check(root@s), SubjectIDs
@@ -267,6 +428,20 @@ class Subjects:
         return self.list_subjects_batch([(namespace, object, relation)], kind)[0]
 
 
+class HostSubjects(_SubjectPages):
+    """Subjects' paged calls on the CPU: host_subjects' ascending lists, sliced"""
+
+    def __init__(self, snapshot):
+        self.snapshot = snapshot
+
+    def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100):
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        n_nodes = self.snapshot.stats()["num_nodes"]
+        invalid = [r >= n_nodes and r != L.NODE_NONE for r in roots]
+        lists = [None if bad else host_subjects(self.snapshot, int(r), cls) for r, bad in zip(roots, invalid)]
+        return _host_pages(lists, invalid, from_ids, limit)
+
+
 def host_list_subjects(snapshot, namespace, object, relation, kind="ids"):
     """ListSubjects on the CPU (host_subjects)"""
     cls = _class_of_kind(snapshot, kind)
@@ -278,4 +453,5 @@ def host_list_subjects(snapshot, namespace, object, relation, kind="ids"):
 
 __all__ = ["Lookup", "host_lookup", "host_list_objects", "resolve_subjects", "Subjects", "host_subjects",
            "host_list_subjects", "resolve_roots", "TYPE_ANY", "TYPE_NONE", "CLASS_SUBJECT_ID", "CLASS_UNTYPED_SET",
-           "TRUNCATED", "INVALID", "SubjectID", "SubjectSet"]
+           "TRUNCATED", "INVALID", "SubjectID", "SubjectSet", "HostLookup", "HostSubjects", "PAGE_LIMIT_MAX",
+           "PAGE_INVALID", "parse_page_token", "check_page_size", "next_page_token"]
