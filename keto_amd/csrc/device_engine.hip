@@ -143,14 +143,16 @@ __device__ __forceinline__ void push_one(const DevGraph &g, const DevState &s, u
 }
 
 // ------------------------------------------------------------------- seed
+// sel: the request bits of every word that this round runs (all ones, or a subset of a
+// one-word round that is run in passes: Engine::split_word)
 __global__ __launch_bounds__(kBlock) void seed_kernel(DevGraph g, DevState s, const uint32_t *roots,
                                                       const uint32_t *targets, uint64_t c0, uint64_t n,
-                                                      uint64_t *flags) {
+                                                      uint64_t *flags, uint64_t sel) {
     const int lane = threadIdx.x & 63;
     uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;  // request index within the round
     bool want = false;
     uint64_t key = 0, deg = 0, mask = 0;
-    if (i < n) {
+    if (i < n && ((sel >> (i & 63)) & 1ull)) {
         uint32_t r = roots[c0 + i], t = targets[c0 + i];
         if (r < g.Nx && t != KETOGPU_NODE_NONE) {
             uint64_t d = g.fint_off[r + 1] - g.fint_off[r];
@@ -180,9 +182,10 @@ __global__ __launch_bounds__(kBlock) void seed_dynamic_kernel(DevGraph g, DevSta
                                                               const uint32_t *targets, uint64_t c0, uint64_t n,
                                                               const uint64_t *dyn_int_off, const uint32_t *dyn_int,
                                                               const uint32_t *dyn_amb, uint64_t *flags,
-                                                              uint64_t base1, unsigned long long *ctr1) {
+                                                              uint64_t base1, unsigned long long *ctr1,
+                                                              uint64_t sel) {
     uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || !((sel >> (i & 63)) & 1ull)) return;
     uint32_t r = roots[c0 + i], t = targets[c0 + i];
     if (r < kDynBase || r == KETOGPU_NODE_NONE || t == KETOGPU_NODE_NONE) return;
     uint32_t k = r - kDynBase, w = (uint32_t)(i >> 6);
@@ -283,12 +286,12 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(DevGraph g, DevState s, 
 // ------------------------------------------------------------------- pull
 __global__ __launch_bounds__(kBlock) void pull_kernel(DevGraph g, DevState s, const uint32_t *roots, const uint32_t *targets,
                                                       uint64_t c0, uint64_t n, const uint64_t *dyn_full_off,
-                                                      const uint32_t *dyn_full, uint64_t *allowed) {
+                                                      const uint32_t *dyn_full, uint64_t *allowed, uint64_t sel) {
     const int lane = threadIdx.x & 63;
     uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     bool ok = false;
     uint64_t examined = 0;
-    if (i < n) {
+    if (i < n && ((sel >> (i & 63)) & 1ull)) {
         uint32_t r = roots[c0 + i], t = targets[c0 + i];
         if (r != KETOGPU_NODE_NONE && t != KETOGPU_NODE_NONE) {
             const uint64_t *vrow = s.vis + (size_t)(i >> 6) * g.Ni;
@@ -341,11 +344,23 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(uint64_t *vis, uint32_t N
 }
 
 // hub index build: the closures of the round's requests (hubs w0*64 ...) into hub_mask
+// (add: a word run in passes over subsets of its hubs ORs each pass's bits in; hub_mask
+// starts zeroed)
 __global__ __launch_bounds__(kBlock) void hub_mask_kernel(const uint64_t *vis, uint32_t Ni, uint64_t nw, uint32_t w0,
-                                                          uint32_t hub_words, uint64_t *hub_mask) {
+                                                          uint32_t hub_words, uint64_t *hub_mask, bool add) {
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < nw * Ni; i += (uint64_t)gridDim.x * kBlock) {
         const uint64_t w = i / Ni, v = i - w * Ni;
-        hub_mask[v * hub_words + w0 + w] = vis[i];
+        const uint64_t old = add ? hub_mask[v * hub_words + w0 + w] : 0;
+        hub_mask[v * hub_words + w0 + w] = old | vis[i];
+    }
+}
+
+// a pass of a split word (Engine::split_word): its result and flag words (tmp[0], tmp[1])
+// OR-ed into the batch's
+__global__ void merge_word_kernel(const uint64_t *tmp, uint64_t *allowed, uint64_t *flags) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        *allowed |= tmp[0];
+        *flags |= tmp[1];
     }
 }
 
@@ -5167,6 +5182,7 @@ struct ketogpu_engine {
     uint32_t *spill_units = nullptr, *spill_roots = nullptr, *spill_targets = nullptr;
     uint64_t *spill_allowed = nullptr, *spill_flags = nullptr;
     unsigned int *spill_count = nullptr;
+    uint64_t *word_tmp = nullptr;  // split_word's scratch result and flag words
 
     bool cascade_log = getenv("KETOGPU_CASCADE_LOG") != nullptr;  // per-stage spill counts on stderr
     // hub index (choose_hubs / build_hubs): hubs are the interior nodes with the most
@@ -5551,7 +5567,14 @@ struct ketogpu_engine {
         // per 4/8/16 requests.  Spills go on to 4-request and 1-request units, then the
         // global path.
         const char *plan = getenv("KETOGPU_UNITS");
-        std::string p = plan ? plan : "auto";
+        std::string p = plan && *plan ? plan : "auto";
+        {
+            static const char *const known[] = {"auto", "bidi", "v2", "lite", "lite32", "core", "label",
+                                                "b16", "w4", "w8", "w16"};
+            if (std::find(std::begin(known), std::end(known), p) == std::end(known))
+                throw Error(KETOGPU_EINVAL, "KETOGPU_UNITS: unknown plan \"" + p +
+                                                "\" (auto|bidi|v2|lite|lite32|core|label|b16|w4|w8|w16)");
+        }
         wave_u = p == "w4" ? 4 : p == "w8" ? 8 : p == "w16" ? 16 : 0;
         const bool lite_req = p == "lite" || p == "lite32" || p == "core" || p == "label" || p == "auto";
         use_v2 = p == "v2" || p == "bidi" || lite_req;
@@ -5711,8 +5734,14 @@ struct ketogpu_engine {
         Wmax = std::max<uint64_t>(1, (budget - std::min(budget, lists)) / per_word);
         if (o && o->max_words_per_round) Wmax = std::min<uint64_t>(Wmax, o->max_words_per_round);
         Wmax = std::min<uint64_t>(Wmax, 1u << 20);
-        // a round appends each (word, node) pair at most once (plus its seeds), so a round of
-        // W <= fe_cap / (Ni + 64) words never overflows the lists (no retries at any degree)
+        // A round appends a (word, node) pair once per level in which new request bits reach
+        // the node (gather_kernel zeroes nxt[slot] after every level), so a word needs up to
+        // 64 entries per interior node, not one.  W <= fe_cap / (Ni + 64) words is the width at
+        // which a round fits when every pair is reached in one level (the common case: closures
+        // of a word overlap little or arrive together); a round that needs more overflows, is
+        // reset densely and retried at half the width (run_global), a single word in passes
+        // over halves of its requests (split_word).  One request alone appends each node at
+        // most once: at most Ni + 1 entries.
         Wmax = std::max<uint64_t>(1, std::min<uint64_t>(Wmax, st.fe_cap / ((uint64_t)s.Ni + 64)));
         size_t state = (size_t)Wmax * std::max<uint32_t>(s.Ni, 1);
         st.vis = dalloc<uint64_t>(state);
@@ -6693,7 +6722,8 @@ struct ketogpu_engine {
     // closures go to hub_mask instead of a pull
     bool round(const Batch &q, uint64_t c0, uint64_t n, ketogpu_run_stats &rs,
                std::vector<std::pair<hipEvent_t, hipEvent_t>> &push_ev,
-               std::vector<std::pair<hipEvent_t, hipEvent_t>> &pull_ev, uint32_t hub_w0 = KETOGPU_NODE_NONE) {
+               std::vector<std::pair<hipEvent_t, hipEvent_t>> &pull_ev, uint32_t hub_w0 = KETOGPU_NODE_NONE,
+               uint64_t sel = ~0ull) {
         const uint64_t W = (n + 63) / 64;
         const uint64_t wg0 = c0 / 64;
         if (st.hub_reach) HIP_CHECK(hipMemsetAsync(st.hub_reach, 0, W * 64 * st.hub_words * 8, stream));
@@ -6701,7 +6731,7 @@ struct ketogpu_engine {
         HIP_CHECK(hipMemsetAsync(st.overflow, 0, sizeof(unsigned int), stream));
         *(uint64_t *)&h_ctr[3] = 0;
         KLAUNCH(seed_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, g, st, q.roots, q.targets, c0, n,
-                           q.flags);
+                           q.flags, sel);
         read_counters();
         uint64_t cnt = h_ctr[0] >> kCntShift, edges = h_ctr[0] & kPreMask;
         std::vector<uint64_t> level_begin{0};
@@ -6709,7 +6739,8 @@ struct ketogpu_engine {
         int cur = 0;  // ctr index of the current level
         if (q.has_dyn) {
             KLAUNCH(seed_dynamic_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, g, st, q.roots,
-                               q.targets, c0, n, q.dyn_int_off, q.dyn_int, q.dyn_amb, q.flags, lb + cnt, &st.ctr[1]);
+                               q.targets, c0, n, q.dyn_int_off, q.dyn_int, q.dyn_amb, q.flags, lb + cnt, &st.ctr[1],
+                               sel);
         }
         bool overflow = (uint32_t)h_ctr[3] != 0;
         for (uint64_t level = 0; !overflow; level++) {
@@ -6755,12 +6786,12 @@ struct ketogpu_engine {
         }
         if (hub_w0 != KETOGPU_NODE_NONE) {
             KLAUNCH(hub_mask_kernel, dim3(std::min<uint64_t>(blocks_for(W * g.Ni), 4096)), dim3(kBlock), 0, stream,
-                    st.vis, g.Ni, W, hub_w0, hub_words, hub_mask);
+                    st.vis, g.Ni, W, hub_w0, hub_words, hub_mask, sel != ~0ull);
         } else {
             hipEvent_t a = ev(), b = ev();
             HIP_CHECK(hipEventRecord(a, stream));
             KLAUNCH(pull_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, g, st, q.roots, q.targets, c0, n,
-                    q.dyn_full_off, q.dyn_full, q.allowed);
+                    q.dyn_full_off, q.dyn_full, q.allowed, sel);
             HIP_CHECK(hipEventRecord(b, stream));
             pull_ev.push_back({a, b});
         }
@@ -6787,11 +6818,58 @@ struct ketogpu_engine {
             uint64_t c0 = w0 * 64, n = std::min<uint64_t>(q.n - c0, wn * 64);
             if (!round(q, c0, n, rs, push_ev, pull_ev, hub_build ? (uint32_t)w0 : KETOGPU_NODE_NONE)) {
                 rs.overflow_retries++;
-                if (wn == 1) throw Error(KETOGPU_ENOMEM, "frontier list overflow for a single 64-request word");
+                if (wn == 1) {
+                    // (the failed round wrote no result word; it zeroed the flag word)
+                    HIP_CHECK(hipMemsetAsync(q.allowed + w0, 0, 8, stream));
+                    split_word(q, c0, n, n == 64 ? ~0ull : (1ull << n) - 1, rs, push_ev, pull_ev,
+                               hub_build ? (uint32_t)w0 : KETOGPU_NODE_NONE);
+                    w0 += 1;
+                    continue;
+                }
                 W = std::max<uint64_t>(1, wn / 2);
                 continue;
             }
             w0 += wn;
+        }
+    }
+
+    // A one-word round that overflowed the lists (a (word, node) pair is appended once per
+    // level in which new request bits reach it, so 64 requests spread along a long chain need
+    // up to 64 entries per node): the word's requests `sel` are run in two passes over half
+    // of them each, a pass that overflows again in halves of its own, down to single
+    // requests.  A pass is a round over a one-word view of the batch whose result and flag
+    // words are scratch words, OR-ed into the batch's words (zero when the first pass starts)
+    // when the pass succeeds (a failed round zeroes its flag words).  KETOGPU_ENOMEM is left for a single request whose own
+    // closure exceeds the lists (more than fe_cap interior nodes).
+    void split_word(const Batch &q, uint64_t c0, uint64_t n, uint64_t sel, ketogpu_run_stats &rs,
+                    std::vector<std::pair<hipEvent_t, hipEvent_t>> &push_ev,
+                    std::vector<std::pair<hipEvent_t, hipEvent_t>> &pull_ev, uint32_t hub_w0) {
+        const int k = __builtin_popcountll(sel);
+        if (k <= 1) throw Error(KETOGPU_ENOMEM, "frontier list overflow for a single request");
+        if (!word_tmp) {
+            word_tmp = dalloc<uint64_t>(2);
+            owned.push_back(word_tmp);
+        }
+        uint64_t lo = 0, rest = sel;
+        for (int i = 0; i < k / 2; i++) {
+            lo |= rest & (~rest + 1);
+            rest &= rest - 1;
+        }
+        Batch v = q;
+        v.roots = q.roots + c0;
+        v.targets = q.targets + c0;
+        v.n = n;
+        v.allowed = word_tmp;
+        v.flags = word_tmp + 1;
+        for (uint64_t part : {lo, rest}) {
+            HIP_CHECK(hipMemsetAsync(word_tmp, 0, 16, stream));
+            if (round(v, 0, n, rs, push_ev, pull_ev, hub_w0, part)) {
+                KLAUNCH(merge_word_kernel, dim3(1), dim3(64), 0, stream, word_tmp, q.allowed + c0 / 64,
+                        q.flags + c0 / 64);
+            } else {
+                rs.overflow_retries++;
+                split_word(q, c0, n, part, rs, push_ev, pull_ev, hub_w0);
+            }
         }
     }
 
