@@ -1017,6 +1017,45 @@ int ketogpu_lookup_stats_get(const ketogpu_lookup *l, ketogpu_lookup_stats *out)
 int ketogpu_lookup_ids(ketogpu_lookup *l, const uint32_t *targets, size_t n, uint32_t type, uint32_t *out,
                        uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
 
+/* Why is a check allowed?  For a root r and a target t a PATH is a sequence v0 = r, v1, ...,
+ * vk = t with k >= 1 in which v(i+1) is an entry of the row of v(i) as the check engine sees it,
+ * that is v(i) is in the reverse row of v(i+1).  A path exists exactly when SubjectIsAllowed(r, t)
+ * (r in B(t)); the calls below return ONE path with the fewest hops, any of them when there are
+ * several.  r == t is answered only through a cycle (R2): the path then starts and ends with r
+ * (a self-loop: r, r).  There is no depth cutoff.  A denied pair gives the empty path, and so do
+ * KETOGPU_NODE_NONE in either field and a root in [num_expandable, num_nodes); any other id
+ * >= num_nodes in either field is invalid.  Under wildcard rows (R5) a hop may stand for a
+ * wildcard match rather than a literal tuple.  R4 snapshots are refused with KETOGPU_EINVAL.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.)
+ *
+ * On the host, a breadth-first search over the reverse rows: *ids the path (r ... t), *n its
+ * length (0: not allowed); free *ids with ketogpu_free.  An invalid id: KETOGPU_EINVAL.  Needs no
+ * GPU; the yardstick of ketogpu_lookup_paths. */
+int ketogpu_snapshot_path(const ketogpu_snapshot *s, uint32_t root, uint32_t target, uint32_t **ids, uint64_t *n);
+/* On the device, on the lookup handle (its reverse rows are what is needed; no second upload):
+ * one path per pair (roots[i], targets[i]).  The output contract is that of ketogpu_lookup_ids:
+ * count[i] is the exact number of nodes on path i (hops + 1; 0 for a denied pair); each path
+ * makes one reservation; begin[i] is the offset in `out` of path i, written completely in the
+ * order r ... t, or KETOGPU_LOOKUP_TRUNCATED (it did not fit in `capacity` ids; nothing of it
+ * was written) or KETOGPU_LOOKUP_INVALID (count 0).  *needed = the sum of all counts; capacity 0
+ * with out NULL is the count-only call.  Returns KETOGPU_OK also when paths were truncated.  The
+ * handle behaves as in its other calls (re-upload when ketogpu_snapshot_version has moved,
+ * KETOGPU_EINVAL after the snapshot is freed, one call at a time, the same tier knobs).  A pair
+ * whose root turns up before the LDS set passes set_capacity finishes in tier 1, whatever the
+ * size of B(t).  Path calls do not move ketogpu_lookup_stats; they count here: */
+typedef struct {
+    uint64_t requests;       /* since creation: pairs passed in                            */
+    uint64_t tier1_requests; /* searched and answered by the one-wave LDS kernel           */
+    uint64_t tier2_requests; /* answered by the workgroup-per-request kernel               */
+    uint64_t tier2_rounds;   /* tier-2 launches of path calls                              */
+    uint64_t allowed;        /* pairs with a path                                          */
+    uint64_t ids_produced;   /* sum of the exact path lengths                              */
+    uint64_t truncated_lists;
+} ketogpu_lookup_path_stats;
+int ketogpu_lookup_path_stats_get(const ketogpu_lookup *l, ketogpu_lookup_path_stats *out);
+int ketogpu_lookup_paths(ketogpu_lookup *l, const uint32_t *roots, const uint32_t *targets, size_t n, uint32_t *out,
+                         uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
+
 /* ------------------------------------------------------- subject listing */
 /* "Who can reach this object?" (OpenFGA ListUsers, SpiceDB LookupSubjects).  For a root node r
  * and a class C, subjects(r, C) is the set of nodes t of class C for which SubjectIsAllowed(r, t)

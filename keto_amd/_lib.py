@@ -326,6 +326,15 @@ class LookupStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class LookupPathStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "requests", "tier1_requests", "tier2_requests", "tier2_rounds", "allowed", "ids_produced",
+        "truncated_lists")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # include/ketogpu.h subject listing
 class SubjectsOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("state_budget_bytes", C.c_uint64)]
@@ -477,6 +486,9 @@ SIGNATURES = {
     "ketogpu_subjects_ids": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
     "ketogpu_lookup_page": (C.c_int, [vp, vp, vp, sz, u32, u32, vp, vp, vp, vp]),
     "ketogpu_subjects_page": (C.c_int, [vp, vp, vp, sz, u32, u32, vp, vp, vp, vp]),
+    "ketogpu_snapshot_path": (C.c_int, [vp, u32, u32, C.POINTER(vp), C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_paths": (C.c_int, [vp, vp, vp, sz, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_path_stats_get": (C.c_int, [vp, C.POINTER(LookupPathStats)]),
 }
 
 _lib = None

@@ -24,6 +24,10 @@
 // finish of paged_finish.hpp instead: the `limit` smallest members >= from[i] to the stride
 // out + i * limit, ascending, with the exact count and what remains; no cursor, no truncation.
 //
+// The path call (ketogpu_lookup_paths) searches in the same order with kernels of its own
+// (path_tier1_kernel, path_tier2_kernel below): every first visit records its parent, and the
+// search ends when the root is visited.
+//
 // Every index is validated before it is used: targets against num_nodes before rev_off is
 // touched, row entries against num_expandable before the type array or a bitmap is.
 #include <hip/hip_runtime.h>
@@ -312,6 +316,191 @@ __global__ __launch_bounds__(kT2Block) void lookup_page_tier2_kernel(LGraph g, c
     }
 }
 
+// ---------------------------------------------------------------------- shortest path
+// ketogpu_lookup_paths: one path r = v0, ..., vk = t with the fewest hops, v(i) in rev(v(i+1)).
+// Both closures above visit in level order (tier 1 works its rows first in, first out; tier 2
+// runs level by level between barriers), so the search below is theirs with two additions: each
+// first visit records the node whose row it was found in, and the search stops once r is seen.
+// The first visit of r then lies on a shortest path, and walking the recorded parents from r
+// leads to t.  Only the target's own row records t as a parent: whatever a later expansion of
+// t (t on a cycle) finds was seen in that first row already, so the walk ends at the first t.
+constexpr uint16_t kParTarget = 0xFFFFu;  // tier 1's parent word: seen in the target's own row
+static_assert(kSlotsLds <= kParTarget, "a slot index fits a parent word");
+
+// r and t as ketogpu_lookup_paths classifies them before any row is read
+__device__ inline bool path_trivial(const LGraph &g, uint32_t r, uint32_t t, uint32_t i, uint32_t lane, const LOut &o) {
+    const bool bad = (r >= g.N && r != KETOGPU_NODE_NONE) || (t >= g.N && t != KETOGPU_NODE_NONE);
+    if (!bad && r < g.Nx && t < g.N) return false;
+    if (lane == 0) {  // an id outside the snapshot: INVALID; NONE or a never-expanded root: denied
+        o.begin[i] = bad ? KETOGPU_LOOKUP_INVALID : 0ull;
+        o.count[i] = 0;
+    }
+    return true;
+}
+
+// one thread: reserve `cnt` ids for path i (a denied pair reserves nothing) -> where to write
+// it, or TRUNCATED
+__device__ inline unsigned long long path_reserve(const LOut &o, uint32_t i, uint32_t cnt) {
+    o.count[i] = cnt;
+    if (!cnt) {
+        o.begin[i] = 0;
+        return KETOGPU_LOOKUP_TRUNCATED;
+    }
+    const unsigned long long base = atomicAdd(o.cursor, (unsigned long long)cnt);
+    const bool fits = base + cnt <= o.capacity;
+    o.begin[i] = fits ? base : KETOGPU_LOOKUP_TRUNCATED;
+    if (!fits) atomicAdd(o.truncated, 1ull);
+    return fits ? base : KETOGPU_LOOKUP_TRUNCATED;
+}
+
+// tier 1: lookup_tier1_kernel's set and worklist, a parent word per slot (the slot of the node
+// whose row the member was first seen in, or kParTarget), and the worklist holds slots, so the
+// row at hand knows its own.  A ballot on u == r after every 64-entry step ends the search.
+__global__ __launch_bounds__(64) void path_tier1_kernel(LGraph g, const uint32_t *roots, const uint32_t *targets,
+                                                        uint32_t n, int force_tier2, LOut o, uint32_t *ovf_list,
+                                                        unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint16_t par[kSlotsLds];
+    __shared__ uint16_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = roots[i], t = targets[i];
+    if (path_trivial(g, r, t, i, lane, o)) return;
+    if (force_tier2) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    for (uint32_t s = lane; s < kSlotsLds; s += 64) set[s] = kEmpty;
+    __syncthreads();
+    uint32_t size = 0, head = 0, tail = 0, hit_slot = 0;  // wave-uniform
+    bool over = false, hit = false;
+    uint32_t v = t, pv = kParTarget;
+    for (;;) {
+        const uint64_t b = g.rev_off[v], e = g.rev_off[v + 1];
+        for (uint64_t base = b; base < e && !over && !hit; base += 64) {
+            const uint64_t j = base + lane;
+            const uint32_t u = j < e ? g.rev_col[j] : kEmpty;
+            bool fresh = false;
+            uint32_t s = 0;
+            if (u < g.Nx) {  // (also drops kEmpty) — at most kSetCap + 64 of the 2 x kSetCap slots are
+                             // ever taken, so the probe ends at a free slot
+                s = slot_of(u);
+                for (;;) {
+                    const uint32_t old = atomicCAS(&set[s], kEmpty, u);
+                    if (old == kEmpty) {
+                        fresh = true;
+                        break;
+                    }
+                    if (old == u) break;
+                    s = (s + 1) & (kSlotsLds - 1);
+                }
+            }
+            if (fresh) par[s] = (uint16_t)pv;  // the winner of the compare-and-swap: the first visit
+            const unsigned long long mf = __ballot(fresh), mi = __ballot(fresh && u < g.Ni);
+            if (fresh && u < g.Ni) work[tail + __popcll(mi & ((1ull << lane) - 1))] = (uint16_t)s;
+            tail += __popcll(mi);
+            size += __popcll(mf);
+            const unsigned long long mh = __ballot(u == r);  // (r < Nx: never kEmpty)
+            if (mh) {
+                hit = true;
+                hit_slot = __shfl(s, __ffsll(mh) - 1);
+            }
+            over = size > kSetCap;  // a hit in the same step still finishes here
+        }
+        __syncthreads();  // the worklist entries and parent words of this row are visible to every lane
+        if (hit || over || head == tail) break;
+        pv = work[head++];
+        v = set[pv];
+    }
+    if (!hit && over) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    if (lane != 0) return;
+    uint32_t cnt = 0;  // nodes on the path: the members from r down to the target's row, and t
+    if (hit) {
+        cnt = 2;
+        for (uint32_t s = hit_slot; par[s] != kParTarget; s = par[s]) cnt++;
+    }
+    const unsigned long long base = path_reserve(o, i, cnt);
+    if (base == KETOGPU_LOOKUP_TRUNCATED) return;
+    uint32_t k = 0;
+    for (uint32_t s = hit_slot;; s = par[s]) {
+        o.out[base + k++] = set[s];
+        if (par[s] == kParTarget) break;
+    }
+    o.out[base + k] = t;
+}
+
+// tier 2: lookup_tier2_kernel's slot state plus a parent array of Nx words.  A parent word is
+// valid exactly where the bitmap bit is set (written by the winner of the atomicOr), so the
+// array is never cleared.  The bitmap is all zero on entry and is cleared again on the way out.
+__global__ __launch_bounds__(kT2Block) void path_tier2_kernel(LGraph g, const uint32_t *roots, const uint32_t *targets,
+                                                              LOut o, const uint32_t *ovf_list, uint32_t first,
+                                                              uint32_t *bitmaps, uint64_t bm_words, uint32_t *worklists,
+                                                              uint32_t *parents) {
+    __shared__ unsigned int s_tail, s_hit;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const uint32_t r = roots[i], t = targets[i];
+    uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
+    uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
+    uint32_t *par = parents + (uint64_t)blockIdx.x * g.Nx;
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = kT2Block / 64;
+    if (tid == 0) s_tail = 0, s_hit = 0;
+    __syncthreads();
+    if (t >= g.N || r >= g.Nx) return;  // (tier 1 lists pairs that need a search only)
+    auto visit = [&](uint32_t u, uint32_t v) {
+        if (u >= g.Nx) return;
+        const uint32_t bit = 1u << (u & 31);
+        if (atomicOr(&bm[u >> 5], bit) & bit) return;
+        par[u] = v;  // the winner of the atomicOr: the first visit
+        if (u < g.Ni) wl[atomicAdd(&s_tail, 1u)] = u;  // each interior node enters once: <= Ni entries
+        if (u == r) s_hit = 1;
+    };
+    {  // the target's own row, by the whole workgroup
+        const uint64_t b = g.rev_off[t], e = g.rev_off[t + 1];
+        for (uint64_t j = b + tid; j < e; j += kT2Block) visit(g.rev_col[j], t);
+    }
+    __syncthreads();
+    uint32_t lb = 0, le = s_tail;
+    bool hit = s_hit != 0;
+    while (lb < le && !hit) {  // one level: a wave per row
+        __syncthreads();  // everyone has read s_tail and s_hit before they move
+        for (uint32_t k = lb + wave; k < le; k += nwaves) {
+            const uint32_t v = wl[k];
+            const uint64_t b = g.rev_off[v], e = g.rev_off[v + 1];
+            for (uint64_t j = b + lane; j < e; j += 64) visit(g.rev_col[j], v);
+        }
+        __syncthreads();  // the level is complete: its parent words are visible
+        lb = le;
+        le = s_tail;
+        hit = s_hit != 0;
+    }
+    if (tid == 0) {  // the chain r -> ... -> t: every node on it but t has its bit set
+        uint32_t cnt = 0;
+        if (hit) {
+            uint32_t x = r;
+            cnt = 1;
+            do {
+                x = par[x];
+                cnt++;
+            } while (x != t);
+        }
+        const unsigned long long base = path_reserve(o, i, cnt);
+        if (base != KETOGPU_LOOKUP_TRUNCATED) {
+            uint32_t x = r, k = 0;
+            o.out[base + k++] = x;
+            do {
+                x = par[x];
+                o.out[base + k++] = x;
+            } while (x != t);
+        }
+    }
+    // (the walk reads parent words only: the bitmap may go meanwhile)
+    for (uint64_t w = tid; w < bm_words; w += kT2Block)
+        if (bm[w]) bm[w] = 0;
+}
+
 }  // namespace
 
 struct ketogpu_lookup {
@@ -328,9 +517,12 @@ struct ketogpu_lookup {
     DBuf<uint32_t> d_col, d_type, d_targets, d_ovf, d_out, d_bm, d_wl;
     DBuf<unsigned long long> d_begin, d_count, d_ctr;  // d_ctr: cursor, truncated, overflow count
     DBuf<uint32_t> d_from, d_ret;                       // paged calls: lower bounds, returned
+    DBuf<uint32_t> d_roots, d_par;                      // path calls: roots, tier 2's parent words
     uint32_t slots = 0, slot_max = 0;  // tier 2: allocated slots; what budget and knob allow (0: not yet known)
+    uint32_t path_slots = 0, path_slot_max = 0;  // the same for path calls: a slot has a parent array too
     uint64_t bm_words = 0;
     ketogpu_lookup_stats st{};
+    ketogpu_lookup_path_stats pst{};
 
     // the rows and types of the snapshot's current version (caller holds its shared lock)
     void upload(const Snapshot &s) {
@@ -347,7 +539,10 @@ struct ketogpu_lookup {
             HIP_CHECK(hipMemcpyAsync(d_type.p, types->node_type.data(), types->node_type.size() * 4,
                                      hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        if (s.Nx != g.Nx || s.Ni != g.Ni) slots = 0, slot_max = 0, d_bm.drop(), d_wl.drop();  // tier 2's state follows the sizes
+        if (s.Nx != g.Nx || s.Ni != g.Ni) {  // tier 2's state follows the sizes
+            slots = 0, slot_max = 0, d_bm.drop(), d_wl.drop();
+            path_slots = 0, path_slot_max = 0, d_par.drop();
+        }
         g = LGraph{d_off.p, d_col.p, d_type.p, s.N, s.Nx, s.Ni};
         version = s.version;
         st.uploads++;
@@ -492,11 +687,89 @@ struct ketogpu_lookup {
         st.last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 
+    // tier 2's state for a path call: need_slots' bitmaps and worklists plus Nx parent words per
+    // slot, all three counted against the budget, so a path round may have fewer slots
+    void need_path_slots(uint32_t wanted) {
+        if (!path_slot_max) {
+            const uint64_t words = ((uint64_t)g.Nx + 31) / 32;
+            const uint64_t per = (words + std::max<uint32_t>(g.Ni, 1) + std::max<uint32_t>(g.Nx, 1)) * 4;
+            uint64_t b = budget;
+            if (!b) {
+                size_t fr = 0, tot = 0;
+                HIP_CHECK(hipMemGetInfo(&fr, &tot));
+                b = fr / 8;
+            }
+            path_slot_max = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(b / per, 1), 1024);
+            if (slot_cap) path_slot_max = std::min(path_slot_max, slot_cap);
+        }
+        uint64_t k = 1;
+        while (k < wanted) k *= 2;
+        k = std::min<uint64_t>(k, path_slot_max);
+        if (k <= path_slots) return;
+        path_slots = 0;
+        need_slots((uint32_t)k);
+        k = std::min<uint64_t>(k, slots);  // (at least one)
+        d_par.need(k * std::max<uint32_t>(g.Nx, 1));  // never cleared: a bitmap bit says which words hold
+        path_slots = (uint32_t)k;
+    }
+
+    // ketogpu_lookup_paths: run()'s output contract, one path per (root, target) pair
+    void run_paths(const uint32_t *roots, const uint32_t *targets, size_t n, uint32_t *out, uint64_t capacity,
+                   uint64_t *begin, uint64_t *count, uint64_t *needed) {
+        HIP_CHECK(hipSetDevice(device));
+        refresh();
+        *needed = 0;
+        pst.requests += n;
+        if (!n) return;
+        d_roots.need(n), d_targets.need(n), d_ovf.need(n), d_begin.need(n), d_count.need(n), d_ctr.need(4),
+            d_out.need(capacity);
+        HIP_CHECK(hipMemcpyAsync(d_roots.p, roots, n * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(d_targets.p, targets, n * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemsetAsync(d_ctr.p, 0, 4 * sizeof(unsigned long long), stream));
+        LOut o{d_out.p, capacity, d_begin.p, d_count.p, d_ctr.p, d_ctr.p + 1};
+        unsigned int *ovf_count = (unsigned int *)(d_ctr.p + 2);
+        KLAUNCH(path_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_roots.p, d_targets.p, (uint32_t)n,
+                force_tier2 ? 1 : 0, o, d_ovf.p, ovf_count);
+        unsigned long long ctr[4];
+        HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        const uint32_t ovf = (uint32_t)(ctr[2] & 0xFFFFFFFFu);
+        if (ovf) {
+            need_path_slots(ovf);
+            for (uint32_t first = 0; first < ovf; first += path_slots) {
+                const uint32_t k = std::min<uint32_t>(path_slots, ovf - first);
+                KLAUNCH(path_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_roots.p, d_targets.p, o, d_ovf.p,
+                        first, d_bm.p, bm_words, d_wl.p, d_par.p);
+                pst.tier2_rounds++;
+            }
+            HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
+        }
+        HIP_CHECK(hipMemcpyAsync(begin, d_begin.p, n * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(count, d_count.p, n * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        const uint64_t written = std::min<uint64_t>(ctr[0], capacity);  // every written path ends below both
+        if (written && out) {
+            HIP_CHECK(hipMemcpyAsync(out, d_out.p, written * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        *needed = ctr[0];
+        uint64_t unsearched = 0, allowed = 0;  // pairs answered before any row was read
+        for (size_t i = 0; i < n; i++) {
+            unsearched += roots[i] >= g.Nx || targets[i] >= g.N;
+            allowed += count[i] != 0;
+        }
+        pst.tier2_requests += ovf;
+        pst.tier1_requests += n - ovf - unsearched;
+        pst.allowed += allowed;
+        pst.ids_produced += ctr[0];
+        pst.truncated_lists += ctr[1];
+    }
+
     ~ketogpu_lookup() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
         d_off.drop(), d_col.drop(), d_type.drop(), d_targets.drop(), d_ovf.drop(), d_out.drop(), d_bm.drop(), d_wl.drop();
-        d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop();
+        d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop(), d_roots.drop(), d_par.drop();
     }
 };
 
@@ -577,6 +850,32 @@ int ketogpu_lookup_page(ketogpu_lookup *l, const uint32_t *targets, const uint32
     return guarded([&] {
         std::lock_guard<std::mutex> lk(l->mu);
         l->run_page(targets, from, n, type, limit, out, returned, count, remaining);
+    });
+}
+
+int ketogpu_lookup_path_stats_get(const ketogpu_lookup *l, ketogpu_lookup_path_stats *out) {
+    if (!l || !out) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    std::lock_guard<std::mutex> lk(const_cast<ketogpu_lookup *>(l)->mu);
+    *out = l->pst;
+    return KETOGPU_OK;
+}
+
+int ketogpu_lookup_paths(ketogpu_lookup *l, const uint32_t *roots, const uint32_t *targets, size_t n, uint32_t *out,
+                         uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
+    if (!l || !needed || (n && (!roots || !targets || !begin || !count)) || (capacity && !out)) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    if (n >= (1ull << 31)) {
+        set_last_error("reverse lookup: more than 2^31 - 1 pairs in one call");
+        return KETOGPU_EINVAL;
+    }
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(l->mu);
+        l->run_paths(roots, targets, n, out, capacity, begin, count, needed);
     });
 }
 

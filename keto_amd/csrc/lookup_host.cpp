@@ -5,6 +5,9 @@
 //     states the check contract as allowed(r, t) <=> r in B(t), B(t) the expandable nodes
 //     that reach t in >= 1 edge; listing B(t) answers the reverse question exactly.  Only
 //     interior entries (ids < Ni) have reverse rows, so only they are expanded.
+//   * ketogpu_snapshot_path: one path root ... target with the fewest hops, by the same closure
+//     run breadth first with a parent per first visit (DESIGN.md "Explain").
+#include <unordered_map>
 #include <unordered_set>
 
 #include "lookup.hpp"
@@ -113,6 +116,62 @@ int ketogpu_snapshot_lookup(const ketogpu_snapshot *sp, uint32_t target, uint32_
             row(target);
             for (size_t h = 0; h < work.size(); h++) row(work[h]);
             std::sort(res.begin(), res.end());
+        }
+        uint32_t *p = (uint32_t *)malloc(std::max<size_t>(res.size(), 1) * sizeof(uint32_t));
+        if (!p) throw std::bad_alloc();
+        if (!res.empty()) memcpy(p, res.data(), res.size() * sizeof(uint32_t));
+        *ids = p;
+        *n = res.size();
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
+
+// A breadth-first search from the target over the reverse rows: rows are expanded in the order
+// their nodes were first seen, so the first visit of the root lies on a path with the fewest
+// hops.  parent[u] is the node whose row u was first seen in.
+int ketogpu_snapshot_path(const ketogpu_snapshot *sp, uint32_t root, uint32_t target, uint32_t **ids, uint64_t *n) {
+    if (!sp || !ids || !n) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *ids = nullptr;
+    *n = 0;
+    try {
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        std::shared_lock<std::shared_mutex> rd(s.mu);
+        if (s.has_ambiguous)
+            throw Error(KETOGPU_EINVAL, "reverse lookup: the snapshot has shared Subject.String() keys (R4)");
+        if (target != NONE && target >= s.N) throw Error(KETOGPU_EINVAL, "target outside the snapshot");
+        if (root != NONE && root >= s.N) throw Error(KETOGPU_EINVAL, "root outside the snapshot");
+        std::vector<uint32_t> res;
+        if (target != NONE && root < s.Nx) {
+            std::unordered_map<uint32_t, uint32_t> parent;
+            std::vector<uint32_t> work;
+            bool hit = false;
+            auto row = [&](uint32_t v) {
+                for (uint64_t j = s.rev_off[v]; j < s.rev_off[v + 1] && !hit; j++) {
+                    const uint32_t u = s.rev_col[j];
+                    if (u >= s.Nx || !parent.emplace(u, v).second) continue;
+                    if (u < s.Ni) work.push_back(u);
+                    hit = u == root;
+                }
+            };
+            row(target);
+            for (size_t h = 0; h < work.size() && !hit; h++) row(work[h]);
+            if (hit) {
+                uint32_t x = root;
+                res.push_back(x);
+                do {  // (only the target's own row gives `target` as a parent: the walk ends there)
+                    x = parent.at(x);
+                    res.push_back(x);
+                } while (x != target);
+            }
         }
         uint32_t *p = (uint32_t *)malloc(std::max<size_t>(res.size(), 1) * sizeof(uint32_t));
         if (!p) throw std::bad_alloc();

@@ -10,6 +10,7 @@ caller gets the reference's responses from the new engines:
     POST /check/batch  (new, SURVEY.md 8(f) row 2)    200 {"results": [{"allowed": bool} | {"error": ...}]}
     GET  /list/objects   (new, DESIGN.md "Sorted, paged lists")  200 {"objects": [...], "next_page_token", "total"}
     GET  /list/subjects  (new, same section)                     200 {"subjects": [...], "next_page_token", "total"}
+    GET  /check/explain  (new, DESIGN.md "Explain")  200 {"allowed":true,"path":[...]} | 403 {"allowed":false,"path":[]}
 
 URL parsing restates RelationQuery.FromURLQuery (internal/relationtuple/definitions.go:
 458-493): a bare "subject" key, both subject forms, or an incomplete subject_set are 400;
@@ -165,7 +166,7 @@ class Handler:
     """(status, JSON body) for each route; engines are check.Engine and expand.Engine.  `lookup`
     and `subjects` are any objects with list_objects_page / list_subjects_page (lookup.Lookup /
     lookup.Subjects on the device, lookup.HostLookup / lookup.HostSubjects without one); without
-    them the list routes answer 404."""
+    them the list routes answer 404.  `lookup` also serves /check/explain through its Explain."""
 
     def __init__(self, check_engine: check.Engine, expand_engine: expand.Engine, lookup=None, subjects=None):
         self.check = check_engine
@@ -296,6 +297,26 @@ class Handler:
             return {"subjects": [s.to_dict() for s in items], "next_page_token": nxt, "total": total}
         return self._list(self.subjects, query, call)
 
+    # ---- why a check is allowed (DESIGN.md "Explain")
+    def get_check_explain(self, query):
+        """the query of GET /check -> 200 {"allowed": true, "path": [...]} with one shortest chain
+        of subjects from namespace:object#relation to the subject (each held by the one before
+        it), 403 {"allowed": false, "path": []}"""
+        if self.lookup is None:
+            return self._error(404, "this server has no lookup handle")
+        q = parse_qs(query, keep_blank_values=True) if isinstance(query, str) else query
+        try:
+            t = tuple_from_url(q)
+            path = self.lookup.Explain(t.namespace, t.object, t.relation, t.subject)
+        except BadRequest as e:
+            return self._error(400, str(e))
+        except _lib.KetoError as e:  # a wildcard root without a node
+            if e.code != _lib.EINVAL:
+                raise
+            return self._error(400, str(e))
+        body = {"allowed": bool(path), "path": [s.to_dict() for s in path]}
+        return (200 if path else 403), body
+
 
 def serve(handler: Handler, port: int):  # pragma: no cover - demo harness
     from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
@@ -314,6 +335,8 @@ def serve(handler: Handler, port: int):  # pragma: no cover - demo harness
             u = urlsplit(self.path)
             if u.path == "/check":
                 self._send(*handler.get_check(u.query))
+            elif u.path == "/check/explain":
+                self._send(*handler.get_check_explain(u.query))
             elif u.path == "/expand":
                 self._send(*handler.get_expand(u.query))
             elif u.path == "/list/objects":

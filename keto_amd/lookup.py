@@ -12,6 +12,10 @@ closure F(r) over the rows the check engine sees (DESIGN.md "Subject listing").
 `host_subjects` walks the rows on the CPU; `Subjects` is the device handle
 (keto_amd/csrc/subjects.hip).
 
+"Why is this check allowed?" — SpiceDB's check trace.  `host_path` / `Lookup.Explain` return one
+path root ... target with the fewest hops over the same reverse rows (ketogpu_snapshot_path,
+ketogpu_lookup_paths on the lookup handle; DESIGN.md "Explain").
+
 Both questions also come sorted and paged (ketogpu_lookup_page / ketogpu_subjects_page,
 DESIGN.md "Sorted, paged lists"): `*_page_raw` on ids, `list_*_page` on names with Keto's
 page_size / page_token convention.  The order is by node id.  `HostLookup` / `HostSubjects` are
@@ -177,7 +181,63 @@ def resolve_subjects(snapshot, subjects):
     return targets.copy()
 
 
-class Lookup(_ObjectPages):
+def host_path(snapshot, root, target):
+    """ketogpu_snapshot_path: the node ids (uint32) of one path root ... target with the fewest
+    hops, empty when the check is denied.  No GPU."""
+    p, n = C.c_void_p(), C.c_uint64()
+    lib = snapshot.L
+    L.check(lib.ketogpu_snapshot_path(snapshot.h, int(root), int(target), C.byref(p), C.byref(n)))
+    try:
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n.value,)).copy() if n.value \
+            else np.zeros(0, dtype=np.uint32)
+    finally:
+        lib.ketogpu_free(p)
+
+
+class _Paths:
+    """"why is this check allowed?" over self.path_ids_raw and self.snapshot (DESIGN.md
+    "Explain")"""
+
+    def path_ids(self, roots, targets):
+        """-> one uint32 array per pair: the node ids root ... target of a path with the fewest
+        hops, empty for a denied pair.  The first call uses 8 ids per pair; only the pairs whose
+        paths were truncated are issued again, with capacity = what they need.  An id outside
+        the snapshot raises EINVAL."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        res = [None] * len(roots)
+        idx = np.arange(len(roots))
+        cap = 8 * len(roots)
+        while len(idx):
+            out, begin, count, _ = self.path_ids_raw(roots[idx], targets[idx], cap)
+            if (begin == INVALID).any():
+                k = idx[begin == INVALID][0]
+                raise L.KetoError(L.EINVAL, f"pair ({int(roots[k])}, {int(targets[k])}) is outside the snapshot")
+            done = begin != TRUNCATED
+            for k in np.nonzero(done)[0]:
+                b, c = int(begin[k]), int(count[k])
+                res[idx[k]] = out[b:b + c].copy()
+            cap = int(count[~done].sum())  # exactly what the rest needs: nothing is truncated twice
+            idx = idx[~done]
+        return res
+
+    def explain_batch(self, tuples):
+        """tuples: (namespace, object, relation, subject) -> per tuple the path that allows the
+        check, as the subjects its nodes stand for: the SubjectSet namespace:object#relation
+        first, the subject last, [] when the check is denied.  Each consecutive pair is one hop:
+        the later subject is held by the earlier subject set.  Under wildcard rows (R5) a hop
+        may stand for a wildcard match rather than a literal tuple.  A wildcard query without a
+        snapshot node raises KetoError(EINVAL), as in resolve_roots."""
+        tuples = [tuple(t) for t in tuples]
+        roots = resolve_roots(self.snapshot, [t[:3] for t in tuples])
+        targets = resolve_subjects(self.snapshot, [t[3] for t in tuples])
+        return [[self.snapshot.describe(int(v)) for v in ids] for ids in self.path_ids(roots, targets)]
+
+    def Explain(self, namespace, object, relation, subject):
+        return self.explain_batch([(namespace, object, relation, subject)])[0]
+
+
+class Lookup(_ObjectPages, _Paths):
     """device handle over a snapshot's reverse rows.  A write to a writable snapshot is seen by
     the next call (the rows are uploaded again when the snapshot's version has moved)."""
 
@@ -241,6 +301,29 @@ class Lookup(_ObjectPages):
             idx = idx[~done]
         return res
 
+    def path_stats(self):
+        st = L.LookupPathStats()
+        L.check(self.L.ketogpu_lookup_path_stats_get(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def path_ids_raw(self, roots, targets, capacity=0):
+        """one ketogpu_lookup_paths call -> (out, begin, count, needed): count[i] the exact
+        number of nodes on path i (0: denied), begin[i] its offset in out, or TRUNCATED /
+        INVALID; capacity 0 only counts"""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        n = len(roots)
+        if len(targets) != n:
+            raise L.KetoError(L.EINVAL, "one target per root")
+        out = np.empty(max(int(capacity), 1), dtype=np.uint32)
+        begin = np.empty(max(n, 1), dtype=np.uint64)
+        count = np.empty(max(n, 1), dtype=np.uint64)
+        needed = C.c_uint64()
+        L.check(self.L.ketogpu_lookup_paths(self.h, roots.ctypes.data, targets.ctypes.data, n,
+                                            out.ctypes.data if capacity else None, int(capacity), begin.ctypes.data,
+                                            count.ctypes.data, C.byref(needed)))
+        return out[:int(capacity)], begin[:n], count[:n], needed.value
+
     def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100):
         """one ketogpu_lookup_page call -> (out[n, limit], returned, count, remaining): row i
         holds the returned[i] smallest members >= from_ids[i], ascending; count[i] the whole
@@ -276,11 +359,38 @@ def host_list_objects(snapshot, namespace, relation, subject):
     return sorted(snapshot.node_info(int(v))["id"] for v in host_lookup(snapshot, t, ty))
 
 
-class HostLookup(_ObjectPages):
-    """Lookup's paged calls on the CPU: host_lookup's ascending lists, sliced"""
+class HostLookup(_ObjectPages, _Paths):
+    """Lookup's paged and path calls on the CPU: host_lookup's ascending lists, sliced, and
+    host_path's paths laid out as the device call lays them out"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def path_ids_raw(self, roots, targets, capacity=0):
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        n = len(roots)
+        if len(targets) != n:
+            raise L.KetoError(L.EINVAL, "one target per root")
+        n_nodes = self.snapshot.stats()["num_nodes"]
+        out = np.zeros(int(capacity), dtype=np.uint32)
+        begin, count = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        cursor = 0
+        for i, (r, t) in enumerate(zip(roots, targets)):
+            if any(v >= n_nodes and v != L.NODE_NONE for v in (r, t)):
+                begin[i] = INVALID
+                continue
+            ids = host_path(self.snapshot, int(r), int(t))
+            count[i] = len(ids)
+            if not len(ids):
+                continue
+            if cursor + len(ids) <= capacity:
+                out[cursor:cursor + len(ids)] = ids
+                begin[i] = cursor
+            else:
+                begin[i] = TRUNCATED
+            cursor += len(ids)  # every path reserves, written or not
+        return out, begin, count, cursor
 
     def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100):
         targets = np.ascontiguousarray(targets, dtype=np.uint32)
@@ -454,4 +564,4 @@ def host_list_subjects(snapshot, namespace, object, relation, kind="ids"):
 __all__ = ["Lookup", "host_lookup", "host_list_objects", "resolve_subjects", "Subjects", "host_subjects",
            "host_list_subjects", "resolve_roots", "TYPE_ANY", "TYPE_NONE", "CLASS_SUBJECT_ID", "CLASS_UNTYPED_SET",
            "TRUNCATED", "INVALID", "SubjectID", "SubjectSet", "HostLookup", "HostSubjects", "PAGE_LIMIT_MAX",
-           "PAGE_INVALID", "parse_page_token", "check_page_size", "next_page_token"]
+           "PAGE_INVALID", "parse_page_token", "check_page_size", "next_page_token", "host_path"]
