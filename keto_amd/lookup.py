@@ -156,16 +156,21 @@ class _SubjectPages:
         return self.list_subjects_page_batch([((namespace, object, relation), page_token)], kind, page_size)[0]
 
 
-def host_lookup(snapshot, target, type_id=TYPE_ANY):
-    """ketogpu_snapshot_lookup: ascending node ids (uint32).  No GPU."""
+def _host_ids(snapshot, call, *args):
+    """one ketogpu_snapshot_* call that answers with a malloc'ed id array -> its copy (uint32)"""
     p, n = C.c_void_p(), C.c_uint64()
     lib = snapshot.L
-    L.check(lib.ketogpu_snapshot_lookup(snapshot.h, int(target), int(type_id), C.byref(p), C.byref(n)))
+    L.check(getattr(lib, call)(snapshot.h, *args, C.byref(p), C.byref(n)))
     try:
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n.value,)).copy() if n.value \
             else np.zeros(0, dtype=np.uint32)
     finally:
         lib.ketogpu_free(p)
+
+
+def host_lookup(snapshot, target, type_id=TYPE_ANY):
+    """ketogpu_snapshot_lookup: ascending node ids (uint32).  No GPU."""
+    return _host_ids(snapshot, "ketogpu_snapshot_lookup", int(target), int(type_id))
 
 
 def resolve_subjects(snapshot, subjects):
@@ -184,14 +189,7 @@ def resolve_subjects(snapshot, subjects):
 def host_path(snapshot, root, target):
     """ketogpu_snapshot_path: the node ids (uint32) of one path root ... target with the fewest
     hops, empty when the check is denied.  No GPU."""
-    p, n = C.c_void_p(), C.c_uint64()
-    lib = snapshot.L
-    L.check(lib.ketogpu_snapshot_path(snapshot.h, int(root), int(target), C.byref(p), C.byref(n)))
-    try:
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n.value,)).copy() if n.value \
-            else np.zeros(0, dtype=np.uint32)
-    finally:
-        lib.ketogpu_free(p)
+    return _host_ids(snapshot, "ketogpu_snapshot_path", int(root), int(target))
 
 
 class _Paths:
@@ -205,21 +203,9 @@ class _Paths:
         the snapshot raises EINVAL."""
         roots = np.ascontiguousarray(roots, dtype=np.uint32)
         targets = np.ascontiguousarray(targets, dtype=np.uint32)
-        res = [None] * len(roots)
-        idx = np.arange(len(roots))
-        cap = 8 * len(roots)
-        while len(idx):
-            out, begin, count, _ = self.path_ids_raw(roots[idx], targets[idx], cap)
-            if (begin == INVALID).any():
-                k = idx[begin == INVALID][0]
-                raise L.KetoError(L.EINVAL, f"pair ({int(roots[k])}, {int(targets[k])}) is outside the snapshot")
-            done = begin != TRUNCATED
-            for k in np.nonzero(done)[0]:
-                b, c = int(begin[k]), int(count[k])
-                res[idx[k]] = out[b:b + c].copy()
-            cap = int(count[~done].sum())  # exactly what the rest needs: nothing is truncated twice
-            idx = idx[~done]
-        return res
+        return _all_lists(lambda idx, cap: self.path_ids_raw(roots[idx], targets[idx], cap), len(roots),
+                          8 * len(roots), False,
+                          lambda k: f"pair ({int(roots[k])}, {int(targets[k])}) is outside the snapshot")
 
     def explain_batch(self, tuples):
         """tuples: (namespace, object, relation, subject) -> per tuple the path that allows the
@@ -237,21 +223,45 @@ class _Paths:
         return self.explain_batch([(namespace, object, relation, subject)])[0]
 
 
-class Lookup(_ObjectPages, _Paths):
-    """device handle over a snapshot's reverse rows.  A write to a writable snapshot is seen by
-    the next call (the rows are uploaded again when the snapshot's version has moved)."""
+def _all_lists(raw, n, cap, sort, invalid):
+    """every list of n requests over a cursor call: raw(idx, cap) -> (out, begin, count, needed)
+    for the requests idx.  Only the requests whose lists were truncated are issued again, with
+    capacity = what they need.  sort: ascending lists (a path keeps its order).  An id outside
+    the snapshot raises EINVAL with the text invalid(request)."""
+    res = [None] * n
+    idx = np.arange(n)
+    while len(idx):
+        out, begin, count, _ = raw(idx, cap)
+        if (begin == INVALID).any():
+            raise L.KetoError(L.EINVAL, invalid(idx[begin == INVALID][0]))
+        done = begin != TRUNCATED
+        for k in np.nonzero(done)[0]:
+            b, c = int(begin[k]), int(count[k])
+            res[idx[k]] = np.sort(out[b:b + c]) if sort else out[b:b + c].copy()
+        cap = int(count[~done].sum())  # exactly what the rest needs: nothing is truncated twice
+        idx = idx[~done]
+    return res
+
+
+class _Handle:
+    """a listing handle of the library over a snapshot: ketogpu_<ABI>_new / _free / _stats_get
+    with the structs OPTS and STATS.  A write to a writable snapshot is seen by the next call
+    (the rows are uploaded again when the snapshot's version has moved)."""
 
     def __init__(self, snapshot, device=0, state_budget_bytes=0):
         self.L = L.lib()
         self.snapshot = snapshot
-        opts = L.LookupOpts(device, state_budget_bytes)
+        opts = self.OPTS(device, state_budget_bytes)
         h = C.c_void_p()
-        L.check(self.L.ketogpu_lookup_new(snapshot.h, C.byref(opts), C.byref(h)))
+        L.check(self._abi("new")(snapshot.h, C.byref(opts), C.byref(h)))
         self.h = h
+
+    def _abi(self, call):
+        return getattr(self.L, f"ketogpu_{self.ABI}_{call}")
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.ketogpu_lookup_free(self.h)
+            self._abi("free")(self.h)
             self.h = None
 
     __del__ = close
@@ -262,77 +272,70 @@ class Lookup(_ObjectPages, _Paths):
     def __exit__(self, *exc):
         self.close()
 
-    def stats(self):
-        st = L.LookupStats()
-        L.check(self.L.ketogpu_lookup_stats_get(self.h, C.byref(st)))
+    def _stats(self, st, call):
+        L.check(self._abi(call)(self.h, C.byref(st)))
         return st.as_dict()
 
-    def lookup_ids_raw(self, targets, type_id=TYPE_ANY, capacity=0):
-        """one ketogpu_lookup_ids call -> (out, begin, count, needed): count[i] exact, begin[i]
-        the offset of list i in out, or TRUNCATED / INVALID; capacity 0 only counts"""
-        targets = np.ascontiguousarray(targets, dtype=np.uint32)
-        n = len(targets)
+    def stats(self):
+        return self._stats(self.STATS(), "stats_get")
+
+    def _ids_raw(self, call, requests, filters, capacity):
+        """one cursor call ketogpu_<ABI>_<call>(handle, *request arrays, n, *filters, ...) ->
+        (out, begin, count, needed): count[i] exact, begin[i] the offset of list i in out, or
+        TRUNCATED / INVALID; capacity 0 only counts"""
+        requests = [np.ascontiguousarray(r, dtype=np.uint32) for r in requests]
+        n = len(requests[0])
         out = np.empty(max(int(capacity), 1), dtype=np.uint32)
         begin = np.empty(max(n, 1), dtype=np.uint64)
         count = np.empty(max(n, 1), dtype=np.uint64)
         needed = C.c_uint64()
-        L.check(self.L.ketogpu_lookup_ids(self.h, targets.ctypes.data, n, int(type_id),
-                                          out.ctypes.data if capacity else None, int(capacity), begin.ctypes.data,
-                                          count.ctypes.data, C.byref(needed)))
+        L.check(self._abi(call)(self.h, *[r.ctypes.data for r in requests], n, *filters,
+                                out.ctypes.data if capacity else None, int(capacity), begin.ctypes.data,
+                                count.ctypes.data, C.byref(needed)))
         return out[:int(capacity)], begin[:n], count[:n], needed.value
+
+    def _page_raw(self, requests, from_ids, filter_id, limit):
+        """one ketogpu_<ABI>_page call -> (out[n, limit], returned, count, remaining): row i
+        holds the returned[i] smallest members >= from_ids[i], ascending; count[i] the whole
+        list's size; returned[i] PAGE_INVALID for an id outside the snapshot"""
+        requests, lo, n, limit, out, returned, count, remaining = _page_args(requests, from_ids, limit)
+        L.check(self._abi("page")(self.h, requests.ctypes.data, None if lo is None else lo.ctypes.data, n,
+                                  int(filter_id), limit, out.ctypes.data, returned.ctypes.data, count.ctypes.data,
+                                  remaining.ctypes.data))
+        return out[:n], returned[:n], count[:n], remaining[:n]
+
+
+class Lookup(_Handle, _ObjectPages, _Paths):
+    """device handle over a snapshot's reverse rows"""
+    ABI, OPTS, STATS = "lookup", L.LookupOpts, L.LookupStats
+
+    def lookup_ids_raw(self, targets, type_id=TYPE_ANY, capacity=0):
+        """one ketogpu_lookup_ids call (_ids_raw)"""
+        return self._ids_raw("ids", [targets], [int(type_id)], capacity)
 
     def lookup_ids(self, targets, type_id=TYPE_ANY, capacity=None):
         """-> one ascending uint32 array per target.  The first call uses `capacity` ids
         (default 64 per target); only the targets whose lists were truncated are issued
         again, with capacity = what they need.  An id outside the snapshot raises EINVAL."""
         targets = np.ascontiguousarray(targets, dtype=np.uint32)
-        res = [None] * len(targets)
-        idx = np.arange(len(targets))
-        cap = 64 * len(targets) if capacity is None else int(capacity)
-        while len(idx):
-            out, begin, count, _ = self.lookup_ids_raw(targets[idx], type_id, cap)
-            if (begin == INVALID).any():
-                raise L.KetoError(L.EINVAL, f"target {int(targets[idx][begin == INVALID][0])} is outside the snapshot")
-            done = begin != TRUNCATED
-            for k in np.nonzero(done)[0]:
-                b, c = int(begin[k]), int(count[k])
-                res[idx[k]] = np.sort(out[b:b + c])
-            cap = int(count[~done].sum())  # exactly what the rest needs: nothing is truncated twice
-            idx = idx[~done]
-        return res
+        return _all_lists(lambda idx, cap: self.lookup_ids_raw(targets[idx], type_id, cap), len(targets),
+                          64 * len(targets) if capacity is None else int(capacity), True,
+                          lambda k: f"target {int(targets[k])} is outside the snapshot")
 
     def path_stats(self):
-        st = L.LookupPathStats()
-        L.check(self.L.ketogpu_lookup_path_stats_get(self.h, C.byref(st)))
-        return st.as_dict()
+        return self._stats(L.LookupPathStats(), "path_stats_get")
 
     def path_ids_raw(self, roots, targets, capacity=0):
         """one ketogpu_lookup_paths call -> (out, begin, count, needed): count[i] the exact
         number of nodes on path i (0: denied), begin[i] its offset in out, or TRUNCATED /
         INVALID; capacity 0 only counts"""
-        roots = np.ascontiguousarray(roots, dtype=np.uint32)
-        targets = np.ascontiguousarray(targets, dtype=np.uint32)
-        n = len(roots)
-        if len(targets) != n:
+        if len(targets) != len(roots):
             raise L.KetoError(L.EINVAL, "one target per root")
-        out = np.empty(max(int(capacity), 1), dtype=np.uint32)
-        begin = np.empty(max(n, 1), dtype=np.uint64)
-        count = np.empty(max(n, 1), dtype=np.uint64)
-        needed = C.c_uint64()
-        L.check(self.L.ketogpu_lookup_paths(self.h, roots.ctypes.data, targets.ctypes.data, n,
-                                            out.ctypes.data if capacity else None, int(capacity), begin.ctypes.data,
-                                            count.ctypes.data, C.byref(needed)))
-        return out[:int(capacity)], begin[:n], count[:n], needed.value
+        return self._ids_raw("paths", [roots, targets], [], capacity)
 
     def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100):
-        """one ketogpu_lookup_page call -> (out[n, limit], returned, count, remaining): row i
-        holds the returned[i] smallest members >= from_ids[i], ascending; count[i] the whole
-        list's size; returned[i] PAGE_INVALID for an id outside the snapshot"""
-        targets, lo, n, limit, out, returned, count, remaining = _page_args(targets, from_ids, limit)
-        L.check(self.L.ketogpu_lookup_page(self.h, targets.ctypes.data, None if lo is None else lo.ctypes.data, n,
-                                           int(type_id), limit, out.ctypes.data, returned.ctypes.data,
-                                           count.ctypes.data, remaining.ctypes.data))
-        return out[:n], returned[:n], count[:n], remaining[:n]
+        """one ketogpu_lookup_page call (_page_raw)"""
+        return self._page_raw(targets, from_ids, type_id, limit)
 
     # ---- names
     def _objects(self, ids):
@@ -402,14 +405,7 @@ class HostLookup(_ObjectPages, _Paths):
 
 def host_subjects(snapshot, root, cls=TYPE_ANY):
     """ketogpu_snapshot_subjects: ascending node ids (uint32).  No GPU."""
-    p, n = C.c_void_p(), C.c_uint64()
-    lib = snapshot.L
-    L.check(lib.ketogpu_snapshot_subjects(snapshot.h, int(root), int(cls), C.byref(p), C.byref(n)))
-    try:
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n.value,)).copy() if n.value \
-            else np.zeros(0, dtype=np.uint32)
-    finally:
-        lib.ketogpu_free(p)
+    return _host_ids(snapshot, "ketogpu_snapshot_subjects", int(root), int(cls))
 
 
 def resolve_roots(snapshot, objects):
@@ -448,79 +444,26 @@ def _subjects_of(snapshot, ids):
     return users + sets
 
 
-class Subjects(_SubjectPages):
-    """device handle over a snapshot's forward rows.  A write to a writable snapshot is seen by
-    the next call (the rows are uploaded again when the snapshot's version has moved)."""
-
-    def __init__(self, snapshot, device=0, state_budget_bytes=0):
-        self.L = L.lib()
-        self.snapshot = snapshot
-        opts = L.SubjectsOpts(device, state_budget_bytes)
-        h = C.c_void_p()
-        L.check(self.L.ketogpu_subjects_new(snapshot.h, C.byref(opts), C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.ketogpu_subjects_free(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def stats(self):
-        st = L.SubjectsStats()
-        L.check(self.L.ketogpu_subjects_stats_get(self.h, C.byref(st)))
-        return st.as_dict()
+class Subjects(_Handle, _SubjectPages):
+    """device handle over a snapshot's forward rows"""
+    ABI, OPTS, STATS = "subjects", L.SubjectsOpts, L.SubjectsStats
 
     def subject_ids_raw(self, roots, cls=TYPE_ANY, capacity=0):
-        """one ketogpu_subjects_ids call -> (out, begin, count, needed): count[i] exact, begin[i]
-        the offset of list i in out, or TRUNCATED / INVALID; capacity 0 only counts"""
-        roots = np.ascontiguousarray(roots, dtype=np.uint32)
-        n = len(roots)
-        out = np.empty(max(int(capacity), 1), dtype=np.uint32)
-        begin = np.empty(max(n, 1), dtype=np.uint64)
-        count = np.empty(max(n, 1), dtype=np.uint64)
-        needed = C.c_uint64()
-        L.check(self.L.ketogpu_subjects_ids(self.h, roots.ctypes.data, n, int(cls),
-                                            out.ctypes.data if capacity else None, int(capacity), begin.ctypes.data,
-                                            count.ctypes.data, C.byref(needed)))
-        return out[:int(capacity)], begin[:n], count[:n], needed.value
+        """one ketogpu_subjects_ids call (_ids_raw)"""
+        return self._ids_raw("ids", [roots], [int(cls)], capacity)
 
     def subject_ids(self, roots, cls=TYPE_ANY, capacity=None):
         """-> one ascending uint32 array per root.  The first call uses `capacity` ids (default
         64 per root); only the roots whose lists were truncated are issued again, with
         capacity = what they need.  An id outside the snapshot raises EINVAL."""
         roots = np.ascontiguousarray(roots, dtype=np.uint32)
-        res = [None] * len(roots)
-        idx = np.arange(len(roots))
-        cap = 64 * len(roots) if capacity is None else int(capacity)
-        while len(idx):
-            out, begin, count, _ = self.subject_ids_raw(roots[idx], cls, cap)
-            if (begin == INVALID).any():
-                raise L.KetoError(L.EINVAL, f"root {int(roots[idx][begin == INVALID][0])} is outside the snapshot")
-            done = begin != TRUNCATED
-            for k in np.nonzero(done)[0]:
-                b, c = int(begin[k]), int(count[k])
-                res[idx[k]] = np.sort(out[b:b + c])
-            cap = int(count[~done].sum())  # exactly what the rest needs: nothing is truncated twice
-            idx = idx[~done]
-        return res
+        return _all_lists(lambda idx, cap: self.subject_ids_raw(roots[idx], cls, cap), len(roots),
+                          64 * len(roots) if capacity is None else int(capacity), True,
+                          lambda k: f"root {int(roots[k])} is outside the snapshot")
 
     def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100):
-        """one ketogpu_subjects_page call -> (out[n, limit], returned, count, remaining): row i
-        holds the returned[i] smallest members >= from_ids[i], ascending; count[i] the whole
-        list's size; returned[i] PAGE_INVALID for an id outside the snapshot"""
-        roots, lo, n, limit, out, returned, count, remaining = _page_args(roots, from_ids, limit)
-        L.check(self.L.ketogpu_subjects_page(self.h, roots.ctypes.data, None if lo is None else lo.ctypes.data, n,
-                                             int(cls), limit, out.ctypes.data, returned.ctypes.data,
-                                             count.ctypes.data, remaining.ctypes.data))
-        return out[:n], returned[:n], count[:n], remaining[:n]
+        """one ketogpu_subjects_page call (_page_raw)"""
+        return self._page_raw(roots, from_ids, cls, limit)
 
     # ---- names
     def list_subjects_batch(self, roots, kind="ids"):

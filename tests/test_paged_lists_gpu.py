@@ -249,10 +249,12 @@ def test_subjects_list_finish_boundary(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------- slot reuse
+@pytest.mark.parametrize("slots", (1, 2))  # 2: a full round, then a partial one in which slot != request
 @pytest.mark.parametrize("side", SIDES, ids=repr)
-def test_slot_reuse(side, monkeypatch):
+def test_slot_reuse(side, slots, monkeypatch):
     monkeypatch.setenv(side.env + "_TIER", "2")
-    monkeypatch.setenv(side.env + "_SLOTS", "1")
+    monkeypatch.setenv(side.env + "_SLOTS", str(slots))
+    rounds = 3 if slots == 1 else 2  # per call: 3 overflow requests
     snap = structure()
     r = np.array([struct_id(side, "u129", "f129"), struct_id(side, "uc", "c2999", "member"),
                   struct_id(side, "u65", "f65")], dtype=np.uint32)
@@ -265,13 +267,13 @@ def test_slot_reuse(side, monkeypatch):
     with side.handle(snap) as h:
         first = check_page(side, h, r, lo, ANY, 100, want_any)
         st = h.stats()
-        assert st["tier2_rounds"] == 3 and st["tier2_requests"] == 3 and st["slots"] == 1
+        assert st["tier2_rounds"] == rounds and st["tier2_requests"] == 3 and st["slots"] == slots
         again = check_page(side, h, r, lo, ANY, 100, want_any)  # the slot was left clean
         for x, y, k in zip(first[0], again[0], first[1]):
             assert np.array_equal(x[:int(k)], y[:int(k)])
         assert all(np.array_equal(x, y) for x, y in zip(first[1:], again[1:]))
         check_page(side, h, r, None, filt, 100, want)
-        assert h.stats()["tier2_rounds"] == 9 and h.stats()["uploads"] == 1
+        assert h.stats()["tier2_rounds"] == 3 * rounds and h.stats()["uploads"] == 1
 
 
 # ------------------------------------------------------------------- batch sizes and bad ids
