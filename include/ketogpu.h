@@ -1169,6 +1169,71 @@ int ketogpu_subjects_page(ketogpu_subjects *h, const uint32_t *roots, const uint
                           uint32_t limit, uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
                           uint64_t *remaining);
 
+/* ------------------------------------------------------- combined listings */
+/* The list of a PAIR of ids under an operator, computed on the device: who can both submit and
+ * approve (subjects AND), what a can see that b cannot (lookup ANDNOT), what a principal sees
+ * under either of two identities without duplicates (lookup OR).  With M(x) the member set of
+ * the plain call for x under the same filter — lookup(x, type) on the lookup handle,
+ * subjects(x, cls) on the subjects handle —
+ *
+ *   KETOGPU_COMBINE_AND     M = M(a) n M(b)
+ *   KETOGPU_COMBINE_ANDNOT  M = M(a) \ M(b)
+ *   KETOGPU_COMBINE_OR      M = M(a) u M(b)
+ *
+ * M(x) keeps every rule of the plain call: x itself is a member only through a cycle,
+ * placeholders are never listed, there is no depth cutoff, R4 snapshots are refused by the
+ * handle.  A side that the plain call answers before it reads a row (KETOGPU_NODE_NONE; on the
+ * subjects handle also a root in [num_expandable, num_nodes)) is the empty set and the operator
+ * is applied as written: AND gives the empty list, ANDNOT M(a) or the empty list, OR the other
+ * side.  An id >= num_nodes that is not KETOGPU_NODE_NONE, on either side, makes the pair
+ * invalid (KETOGPU_LOOKUP_INVALID / KETOGPU_PAGE_INVALID, count 0).  a == b is legal.  An
+ * operator outside the three gives KETOGPU_EINVAL for the whole call.
+ *
+ * ketogpu_*_combine follows the output contract of ketogpu_lookup_ids word for word (count[i]
+ * exact, one reservation per list, a list written completely or begin[i] TRUNCATED, *needed the
+ * sum of the counts, capacity 0 with out NULL counts only, ids in any order without
+ * duplicates); ketogpu_*_combine_page that of ketogpu_lookup_page (ascending by node id, the
+ * same from / returned / remaining rules and token meaning).  The argument checks are those of
+ * the plain calls, with both id arrays required.
+ *
+ * Tier 1 runs both closures in LDS; a pair either of whose closures passes set_capacity (OR: whose
+ * union does) goes to tier 2, which has a second bitmap per slot.  That buffer is allocated at
+ * the first combined call that overflows and is counted against state_budget_bytes with the
+ * rest of a slot, so a combined round may have fewer slots than a plain one.  The tier knobs of
+ * the handle apply.  Combined calls do not move ketogpu_lookup_stats / ketogpu_subjects_stats;
+ * they count here (invalid pairs, and pairs neither side of which has a row to read, belong to
+ * neither tier):
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+#define KETOGPU_COMBINE_AND 0u
+#define KETOGPU_COMBINE_ANDNOT 1u
+#define KETOGPU_COMBINE_OR 2u
+typedef struct {
+    uint64_t requests;       /* since creation: pairs passed in                            */
+    uint64_t tier1_requests; /* answered by the one-wave LDS kernel                        */
+    uint64_t tier2_requests; /* answered by the workgroup-per-pair kernel                  */
+    uint64_t tier2_rounds;   /* tier-2 launches of combined calls                          */
+    uint64_t ids_produced;   /* sum of the exact list sizes (pages: of returned)           */
+    uint64_t truncated_lists;
+    uint32_t slots;          /* tier 2: pairs per round (0 before the first round)         */
+    double last_call_ms;     /* host wall time of the last combined call                   */
+} ketogpu_combine_stats;
+int ketogpu_lookup_combine_stats_get(const ketogpu_lookup *l, ketogpu_combine_stats *out);
+int ketogpu_subjects_combine_stats_get(const ketogpu_subjects *h, ketogpu_combine_stats *out);
+int ketogpu_lookup_combine(ketogpu_lookup *l, const uint32_t *a, const uint32_t *b, size_t n, uint32_t op,
+                           uint32_t type, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                           uint64_t *needed);
+int ketogpu_lookup_combine_page(ketogpu_lookup *l, const uint32_t *a, const uint32_t *b, const uint32_t *from,
+                                size_t n, uint32_t op, uint32_t type, uint32_t limit,
+                                uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
+                                uint64_t *remaining);
+int ketogpu_subjects_combine(ketogpu_subjects *h, const uint32_t *a, const uint32_t *b, size_t n, uint32_t op,
+                             uint32_t cls, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                             uint64_t *needed);
+int ketogpu_subjects_combine_page(ketogpu_subjects *h, const uint32_t *a, const uint32_t *b, const uint32_t *from,
+                                  size_t n, uint32_t op, uint32_t cls, uint32_t limit,
+                                  uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
+                                  uint64_t *remaining);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

@@ -27,6 +27,8 @@ LOOKUP_TRUNCATED, LOOKUP_INVALID = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE
 CLASS_SUBJECT_ID, CLASS_UNTYPED_SET = 0xFFFFFFFD, 0xFFFFFFFC
 # paged lists: the largest page / returned[i] for an id outside the snapshot
 PAGE_LIMIT_MAX, PAGE_INVALID = 65536, 0xFFFFFFFF
+# combined listings: M(a) AND / ANDNOT / OR M(b)
+COMBINE_AND, COMBINE_ANDNOT, COMBINE_OR = 0, 1, 2
 
 
 class KetoError(Exception):
@@ -351,6 +353,16 @@ class SubjectsStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# include/ketogpu.h combined listings
+class CombineStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "requests", "tier1_requests", "tier2_requests", "tier2_rounds", "ids_produced", "truncated_lists")] + [
+            ("slots", C.c_uint32), ("last_call_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol declared in include/ketogpu.h, with its ctypes signature
 vp, i32, u32, sz = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t
 SIGNATURES = {
@@ -489,6 +501,12 @@ SIGNATURES = {
     "ketogpu_snapshot_path": (C.c_int, [vp, u32, u32, C.POINTER(vp), C.POINTER(C.c_uint64)]),
     "ketogpu_lookup_paths": (C.c_int, [vp, vp, vp, sz, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
     "ketogpu_lookup_path_stats_get": (C.c_int, [vp, C.POINTER(LookupPathStats)]),
+    "ketogpu_lookup_combine": (C.c_int, [vp, vp, vp, sz, u32, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_subjects_combine": (C.c_int, [vp, vp, vp, sz, u32, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_combine_page": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, u32, vp, vp, vp, vp]),
+    "ketogpu_subjects_combine_page": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, u32, vp, vp, vp, vp]),
+    "ketogpu_lookup_combine_stats_get": (C.c_int, [vp, C.POINTER(CombineStats)]),
+    "ketogpu_subjects_combine_stats_get": (C.c_int, [vp, C.POINTER(CombineStats)]),
 }
 
 _lib = None

@@ -104,7 +104,9 @@ struct ListHandle {
     DBuf<uint32_t> d_from, d_ret;      // paged calls: lower bounds, returned
     DBuf<uint32_t> d_bm, d_wl;         // tier 2: a bitmap over `bound` and a worklist of Ni per slot
     DBuf<uint32_t> d_aux;              // ... and the handle's own (paths: parent words; subjects: seen lists)
+    DBuf<uint32_t> d_bm2;              // combined calls: a second bitmap per slot
     uint32_t slots = 0, slot_max = 0;  // tier 2: allocated slots; what budget and knob allow (0: not yet known)
+    uint32_t pair_slots = 0, pair_slot_max = 0;  // `slots` for combined calls: a slot has a second bitmap too
     uint32_t bound = 0;                // the member bound the closures take: the bitmaps span it
     uint64_t bm_words = 0;
 
@@ -115,7 +117,7 @@ struct ListHandle {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
         d_off.drop(), d_col.drop(), d_label.drop(), d_req.drop(), d_req2.drop(), d_ovf.drop(), d_out.drop();
         d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop(), d_bm.drop(), d_wl.drop();
-        d_aux.drop();
+        d_aux.drop(), d_bm2.drop();
     }
 
     double ms_of_call() const {
@@ -133,6 +135,7 @@ struct ListHandle {
         HIP_CHECK(hipStreamSynchronize(stream));
         const bool moved = new_bound != bound || s.Ni != g.Ni;
         if (moved) slots = 0, slot_max = 0, d_bm.drop(), d_wl.drop(), d_aux.drop();
+        if (moved) pair_slots = 0, pair_slot_max = 0, d_bm2.drop();
         g = closure::Rows{d_off.p, d_col.p, d_label.p, s.N, s.Nx, s.Ni};
         bound = new_bound, bm_words = ((uint64_t)bound + 31) / 32;
         version = s.version;
@@ -185,6 +188,22 @@ struct ListHandle {
         if (aux_words) d_aux.need(k * aux_words);
         HIP_CHECK(hipMemsetAsync(d_bm.p, 0, k * std::max<uint64_t>(bm_words, 1) * 4, stream));
         return slots = (uint32_t)k;
+    }
+
+    // tier 2's state for a combined call: need(k)'s slots (the handle's own need_slots: bitmaps,
+    // worklists and whatever else its slots carry, `words` words in all) plus a second bitmap per
+    // slot in d_bm2, zeroed here and left zero by every kernel; all of it counted against the
+    // budget, so a combined round may have fewer slots
+    template <class Need>
+    uint32_t need_pair_slots(uint32_t wanted, uint64_t words, Need &&need) {
+        const uint64_t b2w = std::max<uint64_t>(bm_words, 1);
+        uint64_t k = slots_for(wanted, words + b2w, pair_slot_max);
+        if (k <= pair_slots && pair_slots <= slots) return pair_slots;
+        pair_slots = 0;
+        k = std::min<uint64_t>(k, need((uint32_t)k));  // (at least one)
+        d_bm2.need(k * b2w);
+        HIP_CHECK(hipMemsetAsync(d_bm2.p, 0, k * b2w * 4, stream));
+        return pair_slots = (uint32_t)k;
     }
 
     closure::ListOut list_out(uint64_t capacity) {
@@ -255,12 +274,47 @@ struct ListHandle {
         return t;
     }
 
+    // the second ids of a call with pairs of ids, to d_req2
+    void upload_req2(const uint32_t *req2, size_t n) {
+        if (!n) return;
+        d_req2.need(n);
+        HIP_CHECK(hipMemcpyAsync(d_req2.p, req2, n * 4, hipMemcpyHostToDevice, stream));
+    }
+
+    // run_cursor for pairs (a[i], b[i]): a in d_req, b in d_req2
+    template <class Stats, class Unlisted, class T1, class Need, class T2>
+    Tally run_cursor(Stats &st, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out, uint64_t capacity,
+                     uint64_t *begin, uint64_t *count, uint64_t *needed, Unlisted &&unlisted, T1 &&tier1, Need &&need,
+                     T2 &&tier2) {
+        upload_req2(b, n);
+        return run_cursor(st, a, n, out, capacity, begin, count, needed, unlisted, tier1, need, tier2);
+    }
+
     // a paged call, counted in st (INVALID and NONE ids belong to neither tier).  `from` may be
     // null (all zero).  -> the call's counters
     template <class Stats, class T1, class Need, class T2, class After>
     Tally run_page(Stats &st, const uint32_t *req, const uint32_t *from, size_t n, uint32_t limit, uint32_t *out,
                    uint32_t *returned, uint64_t *count, uint64_t *remaining, T1 &&tier1, Need &&need, T2 &&tier2,
                    After &&after) {
+        return run_page(
+            st, req, from, n, limit, out, returned, count, remaining, [&](size_t i) { return req[i] == NONE; }, tier1,
+            need, tier2, after);
+    }
+
+    // run_page for pairs (a[i], b[i]): a in d_req, b in d_req2
+    template <class Stats, class Unlisted, class T1, class Need, class T2, class After>
+    Tally run_page(Stats &st, const uint32_t *a, const uint32_t *b, const uint32_t *from, size_t n, uint32_t limit,
+                   uint32_t *out, uint32_t *returned, uint64_t *count, uint64_t *remaining, Unlisted &&unlisted,
+                   T1 &&tier1, Need &&need, T2 &&tier2, After &&after) {
+        upload_req2(b, n);
+        return run_page(st, a, from, n, limit, out, returned, count, remaining, unlisted, tier1, need, tier2, after);
+    }
+
+    // ... with unlisted(i): a valid request answered before any row was read (see count_call)
+    template <class Stats, class Unlisted, class T1, class Need, class T2, class After>
+    Tally run_page(Stats &st, const uint32_t *req, const uint32_t *from, size_t n, uint32_t limit, uint32_t *out,
+                   uint32_t *returned, uint64_t *count, uint64_t *remaining, Unlisted &&unlisted, T1 &&tier1,
+                   Need &&need, T2 &&tier2, After &&after) {
         Tally t{};
         st.requests += n;
         if (!n) return t;
@@ -277,12 +331,12 @@ struct ListHandle {
         HIP_CHECK(hipMemcpyAsync(remaining, d_begin.p, n * 8, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipMemcpyAsync(out, d_out.p, n * (size_t)limit * 4, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        uint64_t unlisted = 0, produced = 0;
+        uint64_t skipped = 0, produced = 0;
         for (size_t i = 0; i < n; i++) {
-            unlisted += returned[i] == KETOGPU_PAGE_INVALID || req[i] == NONE;
+            skipped += returned[i] == KETOGPU_PAGE_INVALID || unlisted(i);
             produced += returned[i] == KETOGPU_PAGE_INVALID ? 0 : returned[i];
         }
-        count_call(st, t, n, unlisted, produced);
+        count_call(st, t, n, skipped, produced);
         return t;
     }
 };

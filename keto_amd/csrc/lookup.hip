@@ -25,6 +25,7 @@
 // touched, row entries against num_expandable before the type array or a bitmap is.
 #include <hip/hip_runtime.h>
 
+#include "combine.hpp"
 #include "hip_host.hpp"
 #include "lookup.hpp"
 
@@ -284,12 +285,65 @@ __global__ __launch_bounds__(kT2Block) void path_tier2_kernel(Rows g, const uint
         if (bm[w]) bm[w] = 0;
 }
 
+// ---------------------------------------------------------------------- combined listings
+// ketogpu_lookup_combine / _combine_page: lookup(a, T) AND / ANDNOT / OR lookup(b, T).  The
+// bodies are combine.hpp's, over the reverse rows: every id below N has a row, the member bound
+// is Nx.
+__global__ __launch_bounds__(64) void lookup_combine_tier1_kernel(Rows g, const uint32_t *a, const uint32_t *b,
+                                                                  uint32_t n, uint32_t op, uint32_t type,
+                                                                  int force_tier2, ListOut o, uint32_t *ovf_list,
+                                                                  unsigned int *ovf_count) {
+    __shared__ uint32_t set_a[kSlotsLds], set_b[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    combine::tier1_list(g, g.Nx, g.N, a, b, i, lane, op, force_tier2, o, ovf_list, ovf_count, set_a, set_b, work,
+                        [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
+__global__ __launch_bounds__(kT2Block) void lookup_combine_tier2_kernel(Rows g, const uint32_t *a, const uint32_t *b,
+                                                                        uint32_t op, uint32_t type, ListOut o,
+                                                                        const uint32_t *ovf_list, uint32_t first,
+                                                                        uint32_t *bitmaps, uint32_t *bitmaps2,
+                                                                        uint64_t bm_words, uint32_t *worklists) {
+    __shared__ combine::T2Lds s;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    combine::tier2_list(g, g.Nx, g.N, a[i], b[i], i, op, o, bitmaps + (uint64_t)blockIdx.x * bm_words,
+                        bitmaps2 + (uint64_t)blockIdx.x * bm_words, bm_words, worklists + (uint64_t)blockIdx.x * g.Ni,
+                        s, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
+__global__ __launch_bounds__(64) void lookup_combine_page_tier1_kernel(Rows g, const uint32_t *a, const uint32_t *b,
+                                                                       const uint32_t *from, uint32_t n, uint32_t op,
+                                                                       uint32_t type, int force_tier2,
+                                                                       paged::PageOut o, uint32_t *ovf_list,
+                                                                       unsigned int *ovf_count) {
+    __shared__ uint32_t set_a[kSlotsLds], set_b[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    combine::tier1_page(g, g.Nx, g.N, a, b, from, i, lane, op, force_tier2, o, ovf_list, ovf_count, set_a, set_b,
+                        work, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
+__global__ __launch_bounds__(kT2Block) void lookup_combine_page_tier2_kernel(
+    Rows g, const uint32_t *a, const uint32_t *b, const uint32_t *from, uint32_t op, uint32_t type, paged::PageOut o,
+    const uint32_t *ovf_list, uint32_t first, uint32_t *bitmaps, uint32_t *bitmaps2, uint64_t bm_words,
+    uint32_t *worklists) {
+    __shared__ combine::T2Lds s;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    combine::tier2_page(g, g.Nx, g.N, a[i], b[i], from[i], i, op, o, bitmaps + (uint64_t)blockIdx.x * bm_words,
+                        bitmaps2 + (uint64_t)blockIdx.x * bm_words, bm_words, worklists + (uint64_t)blockIdx.x * g.Ni,
+                        s, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
 }  // namespace
 
 struct ketogpu_lookup : ListHandle {
     uint32_t path_slots = 0, path_slot_max = 0;  // `slots` for path calls: a slot has a parent array too
     ketogpu_lookup_stats st{};
     ketogpu_lookup_path_stats pst{};
+    ketogpu_combine_stats cst{};
 
     ketogpu_lookup() : ListHandle("reverse lookup") {}
 
@@ -305,7 +359,14 @@ struct ketogpu_lookup : ListHandle {
 
     uint64_t slot_words() const { return ((uint64_t)g.Nx + 31) / 32 + std::max<uint32_t>(g.Ni, 1); }
 
-    uint32_t need_slots(uint32_t wanted) { return st.slots = ListHandle::need_slots(wanted, slot_words(), 0); }
+    uint32_t alloc_slots(uint32_t wanted) { return ListHandle::need_slots(wanted, slot_words(), 0); }
+
+    uint32_t need_slots(uint32_t wanted) { return st.slots = alloc_slots(wanted); }
+
+    // tier 2's state for a combined call (ListHandle::need_pair_slots)
+    uint32_t need_combine_slots(uint32_t wanted) {
+        return cst.slots = need_pair_slots(wanted, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+    }
 
     // tier 2's state for a path call: need_slots' bitmaps and worklists plus Nx parent words per
     // slot (d_aux), all three counted against the budget, so a path round may have fewer slots
@@ -375,6 +436,47 @@ struct ketogpu_lookup : ListHandle {
             });
         for (size_t i = 0; i < n; i++) pst.allowed += count[i] != 0;
     }
+
+    // a pair answered before any row was read: no side has one (an INVALID pair is counted by
+    // its marker)
+    bool no_row(uint32_t a, uint32_t b) const { return a >= g.N && b >= g.N; }
+
+    // ketogpu_lookup_combine: run()'s output contract, one list per pair (a, b)
+    void run_combine(const uint32_t *a, const uint32_t *b, size_t n, uint32_t op, uint32_t type, uint32_t *out,
+                     uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
+        run_cursor(
+            cst, a, b, n, out, capacity, begin, count, needed,
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || no_row(a[i], b[i]); },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_combine_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_req2.p,
+                        (uint32_t)n, op, type, force_tier2 ? 1 : 0, list_out(capacity), d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return need_combine_slots(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(lookup_combine_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_req2.p, op, type,
+                        list_out(capacity), d_ovf.p, first, d_bm.p, d_bm2.p, bm_words, d_wl.p);
+            });
+        cst.last_call_ms = ms_of_call();
+    }
+
+    // ketogpu_lookup_combine_page: run_page()'s output contract, one page per pair (a, b)
+    void run_combine_page(const uint32_t *a, const uint32_t *b, const uint32_t *from, size_t n, uint32_t op,
+                          uint32_t type, uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count,
+                          uint64_t *remaining) {
+        ListHandle::run_page(
+            cst, a, b, from, n, limit, out, returned, count, remaining, [&](size_t i) { return no_row(a[i], b[i]); },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_combine_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_req2.p,
+                        d_from.p, (uint32_t)n, op, type, force_tier2 ? 1 : 0, page_out(limit), d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return need_combine_slots(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(lookup_combine_page_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_req2.p,
+                        d_from.p, op, type, page_out(limit), d_ovf.p, first, d_bm.p, d_bm2.p, bm_words, d_wl.p);
+            },
+            [](Tally &) {});
+        cst.last_call_ms = ms_of_call();
+    }
 };
 
 extern "C" {
@@ -410,6 +512,27 @@ int ketogpu_lookup_paths(ketogpu_lookup *l, const uint32_t *roots, const uint32_
                          uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
     return list_call(l, !needed || (n && (!roots || !targets || !begin || !count)) || (capacity && !out), n, "pairs",
                      nullptr, [&] { l->run_paths(roots, targets, n, out, capacity, begin, count, needed); });
+}
+
+int ketogpu_lookup_combine_stats_get(const ketogpu_lookup *l, ketogpu_combine_stats *out) {
+    return list_stats_get(l, &ketogpu_lookup::cst, out);
+}
+
+int ketogpu_lookup_combine(ketogpu_lookup *l, const uint32_t *a, const uint32_t *b, size_t n, uint32_t op,
+                           uint32_t type, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                           uint64_t *needed) {
+    if (l && op > KETOGPU_COMBINE_OR) return einval(l->what + ": an unknown combine operator");
+    return list_call(l, !needed || (n && (!a || !b || !begin || !count)) || (capacity && !out), n, "pairs", nullptr,
+                     [&] { l->run_combine(a, b, n, op, type, out, capacity, begin, count, needed); });
+}
+
+int ketogpu_lookup_combine_page(ketogpu_lookup *l, const uint32_t *a, const uint32_t *b, const uint32_t *from,
+                                size_t n, uint32_t op, uint32_t type, uint32_t limit, uint32_t *out,
+                                uint32_t *returned, uint64_t *count, uint64_t *remaining) {
+    if (l && op > KETOGPU_COMBINE_OR) return einval(l->what + ": an unknown combine operator");
+    return list_call(l, n && (!a || !b || !out || !returned || !count || !remaining), n, "pairs", &limit, [&] {
+        l->run_combine_page(a, b, from, n, op, type, limit, out, returned, count, remaining);
+    });
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 // is touched; row entries against N before the class array or a bitmap is.
 #include <hip/hip_runtime.h>
 
+#include "combine.hpp"
 #include "hip_host.hpp"
 #include "subjects.hpp"
 
@@ -215,6 +216,58 @@ __global__ __launch_bounds__(kT2Block) void subjects_page_tier2_kernel(Rows g, c
     if (tid == 0) atomicAdd(by_list ? list_finishes : scan_finishes, 1ull);
 }
 
+// ---------------------------------------------------------------------- combined listings
+// ketogpu_subjects_combine / _combine_page: subjects(a, C) AND / ANDNOT / OR subjects(b, C).
+// The bodies are combine.hpp's, over the forward rows: the ids below Nx have a row, the member
+// bound is N.  Tier 2 finishes by scan only: the seen list is not used.
+__global__ __launch_bounds__(64) void subjects_combine_tier1_kernel(Rows g, const uint32_t *a, const uint32_t *b,
+                                                                    uint32_t n, uint32_t op, uint32_t cls,
+                                                                    int force_tier2, ListOut o, uint32_t *ovf_list,
+                                                                    unsigned int *ovf_count) {
+    __shared__ uint32_t set_a[kSlotsLds], set_b[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    combine::tier1_list(g, g.N, g.Nx, a, b, i, lane, op, force_tier2, o, ovf_list, ovf_count, set_a, set_b, work,
+                        [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
+__global__ __launch_bounds__(kT2Block) void subjects_combine_tier2_kernel(Rows g, const uint32_t *a, const uint32_t *b,
+                                                                          uint32_t op, uint32_t cls, ListOut o,
+                                                                          const uint32_t *ovf_list, uint32_t first,
+                                                                          uint32_t *bitmaps, uint32_t *bitmaps2,
+                                                                          uint64_t bm_words, uint32_t *worklists) {
+    __shared__ combine::T2Lds s;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    combine::tier2_list(g, g.N, g.Nx, a[i], b[i], i, op, o, bitmaps + (uint64_t)blockIdx.x * bm_words,
+                        bitmaps2 + (uint64_t)blockIdx.x * bm_words, bm_words, worklists + (uint64_t)blockIdx.x * g.Ni,
+                        s, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
+__global__ __launch_bounds__(64) void subjects_combine_page_tier1_kernel(Rows g, const uint32_t *a, const uint32_t *b,
+                                                                         const uint32_t *from, uint32_t n, uint32_t op,
+                                                                         uint32_t cls, int force_tier2,
+                                                                         paged::PageOut o, uint32_t *ovf_list,
+                                                                         unsigned int *ovf_count) {
+    __shared__ uint32_t set_a[kSlotsLds], set_b[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    combine::tier1_page(g, g.N, g.Nx, a, b, from, i, lane, op, force_tier2, o, ovf_list, ovf_count, set_a, set_b,
+                        work, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
+__global__ __launch_bounds__(kT2Block) void subjects_combine_page_tier2_kernel(
+    Rows g, const uint32_t *a, const uint32_t *b, const uint32_t *from, uint32_t op, uint32_t cls, paged::PageOut o,
+    const uint32_t *ovf_list, uint32_t first, uint32_t *bitmaps, uint32_t *bitmaps2, uint64_t bm_words,
+    uint32_t *worklists) {
+    __shared__ combine::T2Lds s;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    combine::tier2_page(g, g.N, g.Nx, a[i], b[i], from[i], i, op, o, bitmaps + (uint64_t)blockIdx.x * bm_words,
+                        bitmaps2 + (uint64_t)blockIdx.x * bm_words, bm_words, worklists + (uint64_t)blockIdx.x * g.Ni,
+                        s, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
 }  // namespace
 
 struct ketogpu_subjects : ListHandle {
@@ -222,6 +275,7 @@ struct ketogpu_subjects : ListHandle {
     std::vector<uint64_t> h_off;          // upload staging
     std::vector<uint32_t> h_col;
     ketogpu_subjects_stats st{};
+    ketogpu_combine_stats cst{};
 
     ketogpu_subjects() : ListHandle("subject listing") {}
 
@@ -241,10 +295,20 @@ struct ketogpu_subjects : ListHandle {
         st.uploads++;
     }
 
-    uint32_t need_slots(uint32_t wanted) {
-        const uint64_t snw = std::max<uint32_t>(list_cap, 1);
-        const uint64_t words = std::max<uint64_t>(((uint64_t)g.N + 31) / 32, 1) + std::max<uint32_t>(g.Ni, 1) + snw;
-        return st.slots = ListHandle::need_slots(wanted, words, snw);
+    uint64_t seen_words() const { return std::max<uint32_t>(list_cap, 1); }
+
+    uint64_t slot_words() const {
+        return std::max<uint64_t>(((uint64_t)g.N + 31) / 32, 1) + std::max<uint32_t>(g.Ni, 1) + seen_words();
+    }
+
+    uint32_t alloc_slots(uint32_t wanted) { return ListHandle::need_slots(wanted, slot_words(), seen_words()); }
+
+    uint32_t need_slots(uint32_t wanted) { return st.slots = alloc_slots(wanted); }
+
+    // tier 2's state for a combined call (ListHandle::need_pair_slots): the handle's slots as
+    // they are, seen lists included, since the plain calls share them
+    uint32_t need_combine_slots(uint32_t wanted) {
+        return cst.slots = need_pair_slots(wanted, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
     }
 
     SOut subjects_out(uint64_t capacity) { return {list_out(capacity), d_ctr.p + 3, d_ctr.p + 4}; }
@@ -283,6 +347,48 @@ struct ketogpu_subjects : ListHandle {
             [&](Tally &t) { read_ctrs(t); }));  // (the finish counters)
     }
 
+    // a pair answered before any row was read: no side has one (an INVALID pair is counted by
+    // its marker)
+    bool no_row(uint32_t a, uint32_t b) const { return a >= g.Nx && b >= g.Nx; }
+
+    // ketogpu_subjects_combine: run()'s output contract, one list per pair (a, b)
+    void run_combine(const uint32_t *a, const uint32_t *b, size_t n, uint32_t op, uint32_t cls, uint32_t *out,
+                     uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
+        run_cursor(
+            cst, a, b, n, out, capacity, begin, count, needed,
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || no_row(a[i], b[i]); },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_combine_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_req2.p,
+                        (uint32_t)n, op, cls, force_tier2 ? 1 : 0, list_out(capacity), d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return need_combine_slots(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(subjects_combine_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_req2.p, op,
+                        cls, list_out(capacity), d_ovf.p, first, d_bm.p, d_bm2.p, bm_words, d_wl.p);
+            });
+        cst.last_call_ms = ms_of_call();
+    }
+
+    // ketogpu_subjects_combine_page: run_page()'s output contract, one page per pair (a, b)
+    void run_combine_page(const uint32_t *a, const uint32_t *b, const uint32_t *from, size_t n, uint32_t op,
+                          uint32_t cls, uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count,
+                          uint64_t *remaining) {
+        ListHandle::run_page(
+            cst, a, b, from, n, limit, out, returned, count, remaining, [&](size_t i) { return no_row(a[i], b[i]); },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_combine_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p,
+                        d_req2.p, d_from.p, (uint32_t)n, op, cls, force_tier2 ? 1 : 0, page_out(limit), d_ovf.p,
+                        ovf_count);
+            },
+            [&](uint32_t ovf) { return need_combine_slots(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(subjects_combine_page_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_req2.p,
+                        d_from.p, op, cls, page_out(limit), d_ovf.p, first, d_bm.p, d_bm2.p, bm_words, d_wl.p);
+            },
+            [](Tally &) {});
+        cst.last_call_ms = ms_of_call();
+    }
+
     void count_finishes(const Tally &t) {
         st.list_finishes += t.ctr[3];
         st.scan_finishes += t.ctr[4];
@@ -317,6 +423,27 @@ int ketogpu_subjects_page(ketogpu_subjects *h, const uint32_t *roots, const uint
                           uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count, uint64_t *remaining) {
     return list_call(h, n && (!roots || !out || !returned || !count || !remaining), n, "roots", &limit,
                      [&] { h->run_page(roots, from, n, cls, limit, out, returned, count, remaining); });
+}
+
+int ketogpu_subjects_combine_stats_get(const ketogpu_subjects *h, ketogpu_combine_stats *out) {
+    return list_stats_get(h, &ketogpu_subjects::cst, out);
+}
+
+int ketogpu_subjects_combine(ketogpu_subjects *h, const uint32_t *a, const uint32_t *b, size_t n, uint32_t op,
+                             uint32_t cls, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                             uint64_t *needed) {
+    if (h && op > KETOGPU_COMBINE_OR) return einval(h->what + ": an unknown combine operator");
+    return list_call(h, !needed || (n && (!a || !b || !begin || !count)) || (capacity && !out), n, "pairs", nullptr,
+                     [&] { h->run_combine(a, b, n, op, cls, out, capacity, begin, count, needed); });
+}
+
+int ketogpu_subjects_combine_page(ketogpu_subjects *h, const uint32_t *a, const uint32_t *b, const uint32_t *from,
+                                  size_t n, uint32_t op, uint32_t cls, uint32_t limit, uint32_t *out,
+                                  uint32_t *returned, uint64_t *count, uint64_t *remaining) {
+    if (h && op > KETOGPU_COMBINE_OR) return einval(h->what + ": an unknown combine operator");
+    return list_call(h, n && (!a || !b || !out || !returned || !count || !remaining), n, "pairs", &limit, [&] {
+        h->run_combine_page(a, b, from, n, op, cls, limit, out, returned, count, remaining);
+    });
 }
 
 }  // extern "C"

@@ -10,6 +10,8 @@ caller gets the reference's responses from the new engines:
     POST /check/batch  (new, SURVEY.md 8(f) row 2)    200 {"results": [{"allowed": bool} | {"error": ...}]}
     GET  /list/objects   (new, DESIGN.md "Sorted, paged lists")  200 {"objects": [...], "next_page_token", "total"}
     GET  /list/subjects  (new, same section)                     200 {"subjects": [...], "next_page_token", "total"}
+    GET  /list/objects/combined, /list/subjects/combined  (new, DESIGN.md "Combined listings")  the same bodies for
+         the list of two subjects / two objects under op = and | andnot | or
     GET  /check/explain  (new, DESIGN.md "Explain")  200 {"allowed":true,"path":[...]} | 403 {"allowed":false,"path":[]}
 
 URL parsing restates RelationQuery.FromURLQuery (internal/relationtuple/definitions.go:
@@ -297,6 +299,59 @@ class Handler:
             return {"subjects": [s.to_dict() for s in items], "next_page_token": nxt, "total": total}
         return self._list(self.subjects, query, call)
 
+    # ---- combined lists (DESIGN.md "Combined listings"): the two routes above with an operator
+    # and a second side; bodies, paging and the 400 / 404 rules are theirs
+    @staticmethod
+    def _op(q):
+        op = _get(q, "op")
+        if op not in ("and", "andnot", "or"):
+            raise BadRequest(f'op {op!r}: expected "and", "andnot" or "or"')
+        return op
+
+    def get_list_objects_combined(self, query):
+        """the query of /list/objects plus op (and | andnot | or) and a second subject,
+        other_subject_id | other_subject_set.namespace|object|relation -> the objects o with
+        Check(o@subject) op Check(o@other subject)"""
+        def call(q, size, token):
+            t = tuple_from_url(q)  # the subject is required
+            op = self._op(q)
+            has_id = "other_" + SUBJECT_ID in q
+            has_ss = ["other_" + k in q for k in SS_KEYS]
+            if has_id and any(has_ss):
+                raise BadRequest("exactly one of other_subject_set or other_subject_id has to be provided")
+            if has_id:
+                other = SubjectID(_get(q, "other_" + SUBJECT_ID))
+            elif all(has_ss):
+                other = SubjectSet(*(_get(q, "other_" + k) for k in SS_KEYS))
+            else:
+                raise BadRequest('the second subject has to be specified: "other_subject_id" or a complete '
+                                 '"other_subject_set.*"')
+            items, nxt, total = self.lookup.list_objects_combined_page(t.namespace, t.relation, t.subject, other, op,
+                                                                       size, token)
+            return {"objects": items, "next_page_token": nxt, "total": total}
+        return self._list(self.lookup, query, call)
+
+    def get_list_subjects_combined(self, query):
+        """the query of /list/subjects plus op (and | andnot | or) and a second object,
+        other_namespace, other_object, other_relation -> the subjects s with
+        Check(object@s) op Check(other object@s)"""
+        def call(q, size, token):
+            kind = _get(q, "kind") or "ids"
+            if kind not in ("ids", "any"):
+                ns, sep, rel = kind.partition("#")
+                if not sep:
+                    raise BadRequest(f'kind {kind!r}: expected "ids", "any" or "namespace#relation"')
+                kind = (ns, rel)
+            op = self._op(q)
+            other = [_get(q, k) for k in ("other_namespace", "other_object", "other_relation")]
+            if any(v is None for v in other):
+                raise BadRequest('the second object has to be specified: "other_namespace", "other_object" and '
+                                 '"other_relation"')
+            root = (_get(q, "namespace") or "", _get(q, "object") or "", _get(q, "relation") or "")
+            items, nxt, total = self.subjects.list_subjects_combined_page(root, tuple(other), op, kind, size, token)
+            return {"subjects": [s.to_dict() for s in items], "next_page_token": nxt, "total": total}
+        return self._list(self.subjects, query, call)
+
     # ---- why a check is allowed (DESIGN.md "Explain")
     def get_check_explain(self, query):
         """the query of GET /check -> 200 {"allowed": true, "path": [...]} with one shortest chain
@@ -343,6 +398,10 @@ def serve(handler: Handler, port: int):  # pragma: no cover - demo harness
                 self._send(*handler.get_list_objects(u.query))
             elif u.path == "/list/subjects":
                 self._send(*handler.get_list_subjects(u.query))
+            elif u.path == "/list/objects/combined":
+                self._send(*handler.get_list_objects_combined(u.query))
+            elif u.path == "/list/subjects/combined":
+                self._send(*handler.get_list_subjects_combined(u.query))
             else:
                 self._send(404, {"error": {"code": 404, "status": "Not Found"}})
 

@@ -21,6 +21,12 @@ DESIGN.md "Sorted, paged lists"): `*_page_raw` on ids, `list_*_page` on names wi
 page_size / page_token convention.  The order is by node id.  `HostLookup` / `HostSubjects` are
 the CPU twins with the same methods: the yardstick of the device calls, and a backend for the
 HTTP routes where there is no GPU.
+
+Two lists under an operator — who can both submit and approve, what one user sees that another
+does not — come from one call as well (ketogpu_lookup_combine / ketogpu_subjects_combine and their
+_page forms, DESIGN.md "Combined listings"): `combine_ids`, `combine_page_raw`,
+`ListObjectsCombined` / `ListSubjectsCombined` with op "and" | "andnot" | "or", on the device
+handles and, as numpy set algebra over the host lists, on the CPU twins.
 """
 import ctypes as C
 
@@ -154,6 +160,160 @@ class _SubjectPages:
         """-> (items, next_page_token, total): at most page_size subjects s with
         Check(namespace:object#relation@s), in node-id order from the token on"""
         return self.list_subjects_page_batch([((namespace, object, relation), page_token)], kind, page_size)[0]
+
+
+# ---- combined listings: M(a) op M(b) (include/ketogpu.h "combined listings", DESIGN.md
+# "Combined listings"), shared by the device handles and their CPU twins
+OP_AND, OP_ANDNOT, OP_OR = L.COMBINE_AND, L.COMBINE_ANDNOT, L.COMBINE_OR
+_OP_NAMES = {"and": OP_AND, "andnot": OP_ANDNOT, "or": OP_OR}
+
+
+def op_id(op):
+    """"and" | "andnot" | "or" -> OP_AND | OP_ANDNOT | OP_OR; a number passes as it is (the
+    library judges it); any other name raises KetoError(EINVAL)"""
+    if isinstance(op, str):
+        if op not in _OP_NAMES:
+            raise L.KetoError(L.EINVAL, f"operator {op!r}: expected 'and', 'andnot' or 'or'")
+        return _OP_NAMES[op]
+    return int(op)
+
+
+def _pair_args(a, b):
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    if len(a) != len(b):
+        raise L.KetoError(L.EINVAL, "one second id per first id")
+    return a, b
+
+
+class _CombineIds:
+    """combine_ids over self.combine_ids_raw"""
+
+    def combine_ids(self, a, b, op, filter_id=TYPE_ANY, capacity=None):
+        """-> one ascending uint32 array per pair (a[i], b[i]): M(a) op M(b) under the type /
+        class filter.  The first call uses `capacity` ids (default 64 per pair); only the pairs
+        whose lists were truncated are issued again, with capacity = what they need.  An id
+        outside the snapshot raises EINVAL."""
+        a, b = _pair_args(a, b)
+        op = op_id(op)
+        return _all_lists(lambda idx, cap: self.combine_ids_raw(a[idx], b[idx], op, filter_id, cap), len(a),
+                          64 * len(a) if capacity is None else int(capacity), True,
+                          lambda k: f"pair ({int(a[k])}, {int(b[k])}) is outside the snapshot")
+
+
+class _ObjectsCombined(_CombineIds):
+    """the named forms of the combined object lists over self.combine_ids / combine_page_raw"""
+
+    def list_objects_combined_batch(self, namespace, relation, subject_pairs, op):
+        """per (subject_a, subject_b): the sorted object names o with
+        Check(namespace:o#relation@subject_a) op Check(namespace:o#relation@subject_b)"""
+        op = op_id(op)
+        pairs = list(subject_pairs)
+        ty = self.snapshot.type_id(namespace, relation)
+        a = resolve_subjects(self.snapshot, [p[0] for p in pairs])
+        b = resolve_subjects(self.snapshot, [p[1] for p in pairs])
+        if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
+            return [[] for _ in pairs]
+        return [sorted(self.snapshot.node_info(int(v))["id"] for v in ids) for ids in self.combine_ids(a, b, op, ty)]
+
+    def ListObjectsCombined(self, namespace, relation, subject_a, subject_b, op):
+        return self.list_objects_combined_batch(namespace, relation, [(subject_a, subject_b)], op)[0]
+
+    def list_objects_combined_page(self, namespace, relation, subject_a, subject_b, op, page_size=100, page_token=""):
+        """-> (items, next_page_token, total): list_objects_page of the combined list"""
+        op = op_id(op)
+        page_size = check_page_size(page_size)
+        lo = np.array([parse_page_token(page_token)], dtype=np.uint32)
+        ty = self.snapshot.type_id(namespace, relation)
+        a = resolve_subjects(self.snapshot, [subject_a])
+        b = resolve_subjects(self.snapshot, [subject_b])
+        if ty == TYPE_NONE:
+            return [], "", 0
+        out, returned, count, remaining = self.combine_page_raw(a, b, op, lo, ty, page_size)
+        k = int(returned[0])
+        names = [self.snapshot.node_info(int(v))["id"] for v in out[0, :k]]
+        return names, next_page_token(out[0], k, remaining[0]), int(count[0])
+
+
+class _SubjectsCombined(_CombineIds):
+    """the named forms of the combined subject lists over self.combine_ids / combine_page_raw;
+    roots are (namespace, object, relation) triples"""
+
+    def list_subjects_combined_batch(self, root_pairs, op, kind="ids"):
+        """per (root_a, root_b): the subjects s with Check(root_a@s) op Check(root_b@s),
+        SubjectIDs then SubjectSets, each sorted"""
+        op = op_id(op)
+        pairs = list(root_pairs)
+        cls = _class_of_kind(self.snapshot, kind)
+        a = resolve_roots(self.snapshot, [tuple(p[0]) for p in pairs])
+        b = resolve_roots(self.snapshot, [tuple(p[1]) for p in pairs])
+        if cls == TYPE_NONE:
+            return [[] for _ in pairs]
+        return [_subjects_of(self.snapshot, v) for v in self.combine_ids(a, b, op, cls)]
+
+    def ListSubjectsCombined(self, root_a, root_b, op, kind="ids"):
+        return self.list_subjects_combined_batch([(root_a, root_b)], op, kind)[0]
+
+    def list_subjects_combined_page(self, root_a, root_b, op, kind="ids", page_size=100, page_token=""):
+        """-> (items, next_page_token, total): list_subjects_page of the combined list"""
+        op = op_id(op)
+        page_size = check_page_size(page_size)
+        lo = np.array([parse_page_token(page_token)], dtype=np.uint32)
+        cls = _class_of_kind(self.snapshot, kind)
+        a = resolve_roots(self.snapshot, [tuple(root_a)])
+        b = resolve_roots(self.snapshot, [tuple(root_b)])
+        if cls == TYPE_NONE:
+            return [], "", 0
+        out, returned, count, remaining = self.combine_page_raw(a, b, op, lo, cls, page_size)
+        k = int(returned[0])
+        subs = [self.snapshot.describe(int(v)) for v in out[0, :k]]
+        return subs, next_page_token(out[0], k, remaining[0]), int(count[0])
+
+
+class _HostCombine:
+    """the combined calls of a CPU twin: numpy set algebra over self._members(x, filter_id), the
+    ascending host list of one side (None: an id outside the snapshot), laid out as the device
+    calls lay their results out"""
+
+    def _combined(self, a, b, op, filter_id):
+        a, b = _pair_args(a, b)
+        op = op_id(op)
+        if op not in (OP_AND, OP_ANDNOT, OP_OR):
+            raise L.KetoError(L.EINVAL, f"unknown combine operator {op}")
+        fn = {OP_AND: np.intersect1d, OP_ANDNOT: np.setdiff1d, OP_OR: np.union1d}[op]
+        lists = []
+        for x, y in zip(a, b):
+            ma, mb = self._members(int(x), filter_id), self._members(int(y), filter_id)
+            lists.append(None if ma is None or mb is None else fn(ma, mb).astype(np.uint32))
+        return lists
+
+    def _side(self, x, filter_id, host):
+        if x >= self.snapshot.stats()["num_nodes"]:
+            return np.zeros(0, dtype=np.uint32) if x == L.NODE_NONE else None
+        return host(self.snapshot, x, filter_id)
+
+    def combine_ids_raw(self, a, b, op, filter_id=TYPE_ANY, capacity=0):
+        lists = self._combined(a, b, op, filter_id)
+        n = len(lists)
+        out = np.zeros(int(capacity), dtype=np.uint32)
+        begin, count = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        cursor = 0
+        for i, ids in enumerate(lists):
+            if ids is None:
+                begin[i] = INVALID
+                continue
+            count[i] = len(ids)
+            if cursor + len(ids) <= capacity:
+                out[cursor:cursor + len(ids)] = ids
+                begin[i] = cursor
+            else:
+                begin[i] = TRUNCATED
+            cursor += len(ids)  # every list reserves, written or not
+        return out, begin, count, cursor
+
+    def combine_page_raw(self, a, b, op, from_ids=None, filter_id=TYPE_ANY, limit=100):
+        lists = self._combined(a, b, op, filter_id)
+        return _host_pages(lists, [ids is None for ids in lists], from_ids, limit)
 
 
 def _host_ids(snapshot, call, *args):
@@ -304,8 +464,28 @@ class _Handle:
                                   remaining.ctypes.data))
         return out[:n], returned[:n], count[:n], remaining[:n]
 
+    # ---- combined listings
+    def combine_stats(self):
+        return self._stats(L.CombineStats(), "combine_stats_get")
 
-class Lookup(_Handle, _ObjectPages, _Paths):
+    def combine_ids_raw(self, a, b, op, filter_id=TYPE_ANY, capacity=0):
+        """one ketogpu_<ABI>_combine call -> (out, begin, count, needed) as _ids_raw returns them,
+        one list per pair (a[i], b[i]); filter_id: the handle's type / class filter"""
+        a, b = _pair_args(a, b)
+        return self._ids_raw("combine", [a, b], [op_id(op), int(filter_id)], capacity)
+
+    def combine_page_raw(self, a, b, op, from_ids=None, filter_id=TYPE_ANY, limit=100):
+        """one ketogpu_<ABI>_combine_page call -> (out[n, limit], returned, count, remaining) as
+        _page_raw returns them, one page per pair (a[i], b[i])"""
+        a, b = _pair_args(a, b)
+        a, lo, n, limit, out, returned, count, remaining = _page_args(a, from_ids, limit)
+        L.check(self._abi("combine_page")(self.h, a.ctypes.data, b.ctypes.data, None if lo is None else lo.ctypes.data,
+                                          n, op_id(op), int(filter_id), limit, out.ctypes.data, returned.ctypes.data,
+                                          count.ctypes.data, remaining.ctypes.data))
+        return out[:n], returned[:n], count[:n], remaining[:n]
+
+
+class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined):
     """device handle over a snapshot's reverse rows"""
     ABI, OPTS, STATS = "lookup", L.LookupOpts, L.LookupStats
 
@@ -362,12 +542,15 @@ def host_list_objects(snapshot, namespace, relation, subject):
     return sorted(snapshot.node_info(int(v))["id"] for v in host_lookup(snapshot, t, ty))
 
 
-class HostLookup(_ObjectPages, _Paths):
-    """Lookup's paged and path calls on the CPU: host_lookup's ascending lists, sliced, and
-    host_path's paths laid out as the device call lays them out"""
+class HostLookup(_ObjectPages, _Paths, _HostCombine, _ObjectsCombined):
+    """Lookup's paged, path and combined calls on the CPU: host_lookup's ascending lists, sliced
+    or combined, and host_path's paths laid out as the device call lays them out"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def _members(self, x, type_id):
+        return self._side(x, type_id, host_lookup)
 
     def path_ids_raw(self, roots, targets, capacity=0):
         roots = np.ascontiguousarray(roots, dtype=np.uint32)
@@ -444,7 +627,7 @@ def _subjects_of(snapshot, ids):
     return users + sets
 
 
-class Subjects(_Handle, _SubjectPages):
+class Subjects(_Handle, _SubjectPages, _SubjectsCombined):
     """device handle over a snapshot's forward rows"""
     ABI, OPTS, STATS = "subjects", L.SubjectsOpts, L.SubjectsStats
 
@@ -481,11 +664,15 @@ class Subjects(_Handle, _SubjectPages):
         return self.list_subjects_batch([(namespace, object, relation)], kind)[0]
 
 
-class HostSubjects(_SubjectPages):
-    """Subjects' paged calls on the CPU: host_subjects' ascending lists, sliced"""
+class HostSubjects(_SubjectPages, _HostCombine, _SubjectsCombined):
+    """Subjects' paged and combined calls on the CPU: host_subjects' ascending lists, sliced or
+    combined"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def _members(self, x, cls):
+        return self._side(x, cls, host_subjects)
 
     def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100):
         roots = np.ascontiguousarray(roots, dtype=np.uint32)
@@ -507,4 +694,5 @@ def host_list_subjects(snapshot, namespace, object, relation, kind="ids"):
 __all__ = ["Lookup", "host_lookup", "host_list_objects", "resolve_subjects", "Subjects", "host_subjects",
            "host_list_subjects", "resolve_roots", "TYPE_ANY", "TYPE_NONE", "CLASS_SUBJECT_ID", "CLASS_UNTYPED_SET",
            "TRUNCATED", "INVALID", "SubjectID", "SubjectSet", "HostLookup", "HostSubjects", "PAGE_LIMIT_MAX",
-           "PAGE_INVALID", "parse_page_token", "check_page_size", "next_page_token", "host_path"]
+           "PAGE_INVALID", "parse_page_token", "check_page_size", "next_page_token", "host_path", "OP_AND", "OP_ANDNOT",
+           "OP_OR", "op_id"]
