@@ -687,11 +687,18 @@ int ketogpu_part_begin(ketogpu_part *p, const uint32_t *roots, const uint32_t *t
 int ketogpu_part_begin_dir(ketogpu_part *p, const uint32_t *roots, const uint32_t *targets, size_t n,
                            int32_t direction);
 /* this step's outgoing records grouped by destination rank into send_dev; counts[world].
-   world > 1: send_dev is complete on return (any stream may read it).  world == 1: the copy
-   is ordered on the partition's stream only; pass send_dev straight to ketogpu_part_apply /
-   _pull_answer (which run on that stream) or call ketogpu_part_sync first. */
+   world > 1: send_dev is complete on return (any stream may read it).  world == 1: the
+   records stay where the kernels wrote them; pass send_dev (and counts[0]) straight to
+   ketogpu_part_apply / _pull_answer, which then read them there, or call ketogpu_part_sync
+   first: it copies them into send_dev for any other reader. */
 int ketogpu_part_emit(ketogpu_part *p, ketogpu_record *send_dev, uint64_t capacity, uint64_t *counts);
-/* OR received records into the owned state; *frontier = owned entries of the next level */
+/* OR received records into the owned state; *frontier = owned entries of the next level.
+   The caller's contract: every record's a is a word of the round (a < ceil(n / 64) of the
+   begin call, so a < round_words) — the kernel indexes the state with it unchecked, a record
+   outside it is an out-of-bounds store.  b is checked: a node this rank does not own as
+   interior (another rank's, a layout gap, an id >= N) fails the call with KETOGPU_EINVAL and
+   *frontier = 0; the round is then left to ketogpu_part_abort.  ketogpu_part_pull_answer
+   checks both fields (a < n of the begin call) and fails the same way. */
 int ketogpu_part_apply(ketogpu_part *p, const ketogpu_record *recv_dev, uint64_t n, uint64_t *frontier);
 /* the owned frontier's rows -> the next emit's records */
 int ketogpu_part_expand(ketogpu_part *p);
@@ -701,7 +708,8 @@ int ketogpu_part_pull_answer(ketogpu_part *p, const ketogpu_record *recv_dev, ui
 /* this rank's hit bits of the round (ceil(n/64) host words) and state reset */
 int ketogpu_part_end(ketogpu_part *p, uint64_t *allowed_bits);
 int ketogpu_part_abort(ketogpu_part *p);
-/* wait for the partition's stream (world 1: makes the last emit's send_dev readable elsewhere) */
+/* wait for the partition's stream (world 1: first copies the last emit's records into its
+   send_dev, which makes them readable elsewhere) */
 int ketogpu_part_sync(ketogpu_part *p);
 int ketogpu_part_stats_get(const ketogpu_part *p, ketogpu_part_stats *out);
 /* on: every kernel launch of the partition is bracketed by hipEvents on its stream (a

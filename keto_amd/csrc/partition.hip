@@ -758,6 +758,7 @@ struct ketogpu_part {
     int pack(ketogpu_record *send, uint64_t capacity, uint64_t *counts) {
         read_ctr();
         const uint64_t n = h[3];
+        obuf_send = nullptr;
         if (overflow_bits() || n > capacity) {
             for (uint32_t g = 0; g < world; g++) counts[g] = 0;
             return overflow_bits() & 4u ? KETOGPU_EINVAL : KETOGPU_ENOMEM;
@@ -907,6 +908,7 @@ struct ketogpu_part {
         if (timing) resolve_timing();
         lb = cnt = edges = 0;
         dirty = false;
+        obuf_send = nullptr;  // a finished round's records are no longer in obuf (ketogpu_part_sync)
     }
 
     void end(uint64_t *bits) {
@@ -1095,6 +1097,13 @@ int ketogpu_part_sync(ketogpu_part *p) {
     if (!p) throw Error(KETOGPU_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(p->mu);
     PHIP(hipSetDevice(p->device));
+    // world 1: the last emit left its records where the kernels wrote them (pack); a reader
+    // other than apply / pull_answer gets them in its send buffer here, and a later apply of
+    // that buffer reads the buffer itself
+    if (p->obuf_send && p->obuf_n)
+        PHIP(hipMemcpyAsync((void *)p->obuf_send, p->P.obuf, p->obuf_n * sizeof(ketogpu_record),
+                            hipMemcpyDeviceToDevice, p->stream));
+    p->obuf_send = nullptr;
     PHIP(hipStreamSynchronize(p->stream));
     PAPI_END
 }

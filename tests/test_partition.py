@@ -6,7 +6,13 @@ CPU tests load real shards (the C++ loader) with world_size 1, 2 and 3 over gloo
 the check protocol with each rank's device steps played by tests/part_cpu.py; they also
 pin the refusals (wildcard subject sets, rows out of order, shared String() keys, hash
 collisions) and that a rank holds about 1/world of the graph.  The GPU tests run the HIP
-steps (partition.hip) with world_size 1 and with two ranks sharing the box's GPU."""
+steps (partition.hip) with world_size 1 and with two ranks sharing the box's GPU.
+
+These tests compare final answers.  The steps themselves — every level's records, counts,
+frontiers and hit bits, at world 1, 2, 3, 5 and 64 in one process — are held against the
+model in tests/test_partition_world_cpu.py (no GPU: the model against the oracle, the raw
+id exchange and its refusals) and tests/test_partition_world_gpu.py (the HIP steps against
+the model); tests/part_world.py has their helpers."""
 import os
 import tempfile
 
