@@ -1242,6 +1242,87 @@ int ketogpu_subjects_combine_page(ketogpu_subjects *h, const uint32_t *a, const 
                                   uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
                                   uint64_t *remaining);
 
+/* -------------------------------------------------- depth-limited listings */
+/* The members of a listing within k hops of its start, computed on the device: "who holds this
+ * document directly, who through one group, who through any chain" is the closure cut at 1, 2
+ * and no limit.  The plain, paged, combined and path calls above have no depth cutoff; these do.
+ *
+ * A listing starts from a node x: the target t of a lookup, the root r of a subject listing.
+ * For a member u, d(x, u) is the number of hops of a shortest path, the one
+ * ketogpu_snapshot_path defines: its count - 1, at least 1.  Level 1 is the set of entries of
+ * x's own row; level d + 1 is what the rows of the interior members of level d add for the
+ * first time.  With M(x) the member set of the plain call under the same type / class filter,
+ *
+ *   M_k(x) = { u in M(x) : d(x, u) <= k }
+ *
+ * x itself is a member only through a cycle of at most k hops, placeholders are never members,
+ * R4 snapshots are refused by the handle, and KETOGPU_NODE_NONE, never-expanded roots and ids
+ * outside the snapshot are classified as in the plain call.
+ *
+ * max_depth is given PER REQUEST, as an array next to the ids: max_depth[i] hops for request i,
+ * KETOGPU_DEPTH_ALL (0) for no limit.  A null array is no limit for every request.  An unlimited
+ * request returns the member set of the plain call (order and offsets are free, as always).
+ *
+ * frontier[i] is the number of interior members (ids < num_interior, as ketogpu_snapshot_graph
+ * reports it for the current version) at distance exactly max_depth[i]: the members whose rows
+ * the limit left unread.  0 means that the list is the
+ * whole closure ("complete"); > 0 means that deeper levels MAY hold more.  It is 0 for every
+ * unlimited request and for every request answered before a row is read.  `frontier` may be null.
+ *
+ * This is NOT Keto's expand at a depth.  BuildTree shares one visited map across a depth-first
+ * walk, so which occurrence of a node is expanded, and with it what a depth cuts off, depends on
+ * row order; here the distance is the breadth-first one and the answer is a set.  No parity with
+ * ketogpu_expand at a max depth is claimed.
+ *
+ * ketogpu_*_ids_depth follows the output contract of ketogpu_lookup_ids word for word (count[i]
+ * exact, one reservation per list, a list written completely or begin[i] TRUNCATED, *needed the
+ * sum of the counts, capacity 0 with out NULL counts only); ketogpu_*_page_depth that of
+ * ketogpu_lookup_page (ascending by node id, the same from / returned / remaining rules and
+ * token meaning; a token belongs to a (request, depth) pair as it belongs to a (request, filter)
+ * pair).  The argument checks are those of the plain calls.  The host calls return their ids
+ * ascending and give KETOGPU_EINVAL for an id outside the snapshot.
+ *
+ * Tier 1 stops before it reads a row of level max_depth, so a request goes to tier 2 exactly
+ * when its unfiltered M_k, not its whole closure, passes set_capacity.  Tier 2 needs no state
+ * beyond the plain calls' slots.  The tier knobs of the handle apply.  Depth calls do not move
+ * ketogpu_lookup_stats / ketogpu_subjects_stats; they count here:
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+#define KETOGPU_DEPTH_ALL 0u
+typedef struct {
+    uint64_t requests;       /* since creation: requests passed in                         */
+    uint64_t tier1_requests; /* answered by the one-wave LDS kernel                        */
+    uint64_t tier2_requests; /* answered by the workgroup-per-request kernel               */
+    uint64_t tier2_rounds;   /* tier-2 launches of depth calls                             */
+    uint64_t list_finishes;  /* subjects handle, tier 2: finished by the seen list ...     */
+    uint64_t scan_finishes;  /* ... and by a scan of the bitmap (both 0 on the lookup handle) */
+    uint64_t cut_requests;   /* requests with a non-zero frontier                          */
+    uint64_t ids_produced;   /* sum of the exact list sizes (pages: of returned)           */
+    uint64_t truncated_lists;
+    uint32_t slots;          /* tier 2: requests per round (0 before the first round)      */
+    double last_call_ms;     /* host wall time of the last depth call                      */
+} ketogpu_depth_stats;
+int ketogpu_lookup_depth_stats_get(const ketogpu_lookup *l, ketogpu_depth_stats *out);
+int ketogpu_subjects_depth_stats_get(const ketogpu_subjects *h, ketogpu_depth_stats *out);
+/* host (no GPU): *ids malloc'ed, ascending, free with ketogpu_free; *frontier may be null */
+int ketogpu_snapshot_lookup_depth(const ketogpu_snapshot *s, uint32_t target, uint32_t type, uint32_t max_depth,
+                                  uint32_t **ids, uint64_t *n, uint64_t *frontier);
+int ketogpu_snapshot_subjects_depth(const ketogpu_snapshot *s, uint32_t root, uint32_t cls, uint32_t max_depth,
+                                    uint32_t **ids, uint64_t *n, uint64_t *frontier);
+int ketogpu_lookup_ids_depth(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth, size_t n,
+                             uint32_t type, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                             uint64_t *frontier, uint64_t *needed);
+int ketogpu_subjects_ids_depth(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth, size_t n,
+                               uint32_t cls, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                               uint64_t *frontier, uint64_t *needed);
+int ketogpu_lookup_page_depth(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth,
+                              const uint32_t *from, size_t n, uint32_t type, uint32_t limit,
+                              uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
+                              uint64_t *remaining, uint64_t *frontier);
+int ketogpu_subjects_page_depth(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth,
+                                const uint32_t *from, size_t n, uint32_t cls, uint32_t limit,
+                                uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
+                                uint64_t *remaining, uint64_t *frontier);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

@@ -363,6 +363,19 @@ class CombineStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# include/ketogpu.h depth-limited listings
+DEPTH_ALL = 0
+
+
+class DepthStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "requests", "tier1_requests", "tier2_requests", "tier2_rounds", "list_finishes", "scan_finishes",
+        "cut_requests", "ids_produced", "truncated_lists")] + [("slots", C.c_uint32), ("last_call_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol declared in include/ketogpu.h, with its ctypes signature
 vp, i32, u32, sz = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t
 SIGNATURES = {
@@ -507,6 +520,16 @@ SIGNATURES = {
     "ketogpu_subjects_combine_page": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, u32, vp, vp, vp, vp]),
     "ketogpu_lookup_combine_stats_get": (C.c_int, [vp, C.POINTER(CombineStats)]),
     "ketogpu_subjects_combine_stats_get": (C.c_int, [vp, C.POINTER(CombineStats)]),
+    "ketogpu_lookup_depth_stats_get": (C.c_int, [vp, C.POINTER(DepthStats)]),
+    "ketogpu_subjects_depth_stats_get": (C.c_int, [vp, C.POINTER(DepthStats)]),
+    "ketogpu_snapshot_lookup_depth": (C.c_int, [vp, u32, u32, u32, C.POINTER(vp), C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_uint64)]),
+    "ketogpu_snapshot_subjects_depth": (C.c_int, [vp, u32, u32, u32, C.POINTER(vp), C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_ids_depth": (C.c_int, [vp, vp, vp, sz, u32, vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_subjects_ids_depth": (C.c_int, [vp, vp, vp, sz, u32, vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_page_depth": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp]),
+    "ketogpu_subjects_page_depth": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

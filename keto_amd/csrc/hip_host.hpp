@@ -16,6 +16,7 @@
 #include <new>
 #include <shared_mutex>
 #include <string>
+#include <vector>
 
 #include "closure.hpp"
 #include "ketogpu_internal.hpp"
@@ -105,6 +106,7 @@ struct ListHandle {
     DBuf<uint32_t> d_bm, d_wl;         // tier 2: a bitmap over `bound` and a worklist of Ni per slot
     DBuf<uint32_t> d_aux;              // ... and the handle's own (paths: parent words; subjects: seen lists)
     DBuf<uint32_t> d_bm2;              // combined calls: a second bitmap per slot
+    DBuf<unsigned long long> d_front;  // depth calls: the frontier per request
     uint32_t slots = 0, slot_max = 0;  // tier 2: allocated slots; what budget and knob allow (0: not yet known)
     uint32_t pair_slots = 0, pair_slot_max = 0;  // `slots` for combined calls: a slot has a second bitmap too
     uint32_t bound = 0;                // the member bound the closures take: the bitmaps span it
@@ -117,7 +119,7 @@ struct ListHandle {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
         d_off.drop(), d_col.drop(), d_label.drop(), d_req.drop(), d_req2.drop(), d_ovf.drop(), d_out.drop();
         d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop(), d_bm.drop(), d_wl.drop();
-        d_aux.drop(), d_bm2.drop();
+        d_aux.drop(), d_bm2.drop(), d_front.drop();
     }
 
     double ms_of_call() const {
@@ -279,6 +281,31 @@ struct ListHandle {
         if (!n) return;
         d_req2.need(n);
         HIP_CHECK(hipMemcpyAsync(d_req2.p, req2, n * 4, hipMemcpyHostToDevice, stream));
+    }
+
+    // a depth call's limits to d_req2 (null: no limit for any request, and the kernels are told
+    // so by a null array), and its frontier words zeroed: a kernel writes the non-zero ones
+    // -> the device array of limits
+    const uint32_t *upload_depth(const uint32_t *max_depth, size_t n) {
+        if (!n) return nullptr;
+        d_front.need(n);
+        HIP_CHECK(hipMemsetAsync(d_front.p, 0, n * 8, stream));
+        if (!max_depth) return nullptr;
+        upload_req2(max_depth, n);
+        return d_req2.p;
+    }
+
+    // ... and the frontier back behind the call (`frontier` may be null) -> requests with a
+    // non-zero frontier
+    uint64_t read_frontier(uint64_t *frontier, size_t n) {
+        if (!n) return 0;
+        std::vector<uint64_t> mine;
+        if (!frontier) mine.resize(n), frontier = mine.data();
+        HIP_CHECK(hipMemcpyAsync(frontier, d_front.p, n * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        uint64_t cut = 0;
+        for (size_t i = 0; i < n; i++) cut += frontier[i] != 0;
+        return cut;
     }
 
     // run_cursor for pairs (a[i], b[i]): a in d_req, b in d_req2

@@ -21,11 +21,16 @@
 // path_tier2_kernel below): every first visit records its parent, and the search ends when
 // the root is visited.
 //
+// The depth calls (ketogpu_lookup_ids_depth / _page_depth) list the members within max_depth[i]
+// hops of the target: the full-list and the paged kernels with depth.hpp's level bookkeeping in
+// the closures and frontier[i], the interior members the limit left unread, next to the count.
+//
 // Every index is validated before it is used: targets against num_nodes before rev_off is
 // touched, row entries against num_expandable before the type array or a bitmap is.
 #include <hip/hip_runtime.h>
 
 #include "combine.hpp"
+#include "depth.hpp"
 #include "hip_host.hpp"
 #include "lookup.hpp"
 
@@ -337,6 +342,111 @@ __global__ __launch_bounds__(kT2Block) void lookup_combine_page_tier2_kernel(
                         s, [&](uint32_t u) { return type_ok(g, u, type); });
 }
 
+// ---------------------------------------------------------------------- depth-limited listings
+// ketogpu_lookup_ids_depth / _page_depth: the members of lookup(t, T) within max_depth[i] hops
+// of t (DESIGN.md "Depth-limited listings").  The kernels of the plain calls with depth.hpp's
+// closure in tier 1 and its LevelStop in tier 2; the finishes are the plain ones.  frontier[i]
+// is all zero on entry and is written where a search stopped at its limit.
+
+// a member under any filter: what the frontier counts (a placeholder has no type)
+__device__ inline bool any_type(const Rows &g, uint32_t u) { return type_ok(g, u, KETOGPU_TYPE_ANY); }
+__global__ __launch_bounds__(64) void lookup_depth_tier1_kernel(Rows g, const uint32_t *targets,
+                                                                const uint32_t *max_depth, uint32_t n, uint32_t type,
+                                                                int force_tier2, ListOut o,
+                                                                unsigned long long *frontier, uint32_t *ovf_list,
+                                                                unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = targets[i];
+    if (t >= g.N) {  // NONE: the empty list; any other id outside the snapshot: INVALID
+        if (lane == 0) {
+            o.begin[i] = t == KETOGPU_NODE_NONE ? 0ull : KETOGPU_LOOKUP_INVALID;
+            o.count[i] = 0;
+        }
+        return;
+    }
+    uint32_t fr = 0;
+    if (force_tier2 || !depth::tier1_closure(g, g.Nx, t, depth::limit_of(max_depth, i), lane, set, work, fr,
+                                              [&](uint32_t u) { return any_type(g, u); })) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    if (lane == 0 && fr) frontier[i] = fr;
+    tier1_finish(set, lane, i, o, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
+__global__ __launch_bounds__(kT2Block) void lookup_depth_tier2_kernel(Rows g, const uint32_t *targets,
+                                                                      const uint32_t *max_depth, uint32_t type,
+                                                                      ListOut o, unsigned long long *frontier,
+                                                                      const uint32_t *ovf_list, uint32_t first,
+                                                                      uint32_t *bitmaps, uint64_t bm_words,
+                                                                      uint32_t *worklists) {
+    __shared__ unsigned int s_tail, s_cnt, s_pos, s_fr;
+    __shared__ unsigned long long s_base;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const uint32_t t = targets[i];
+    uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
+    uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
+    if (threadIdx.x == 0) s_tail = 0, s_cnt = 0, s_pos = 0, s_fr = 0;
+    __syncthreads();
+    if (t >= g.N) return;  // (tier 1 lists valid targets only)
+    depth::LevelStop stop(&s_tail, depth::limit_of(max_depth, i));
+    tier2_closure(g, g.Nx, t, bm, wl, &s_tail, [](uint32_t, uint32_t) {}, depth::LevelStopRef{&stop});
+    depth::tier2_frontier(stop, wl, frontier + i, &s_fr, [&](uint32_t u) { return any_type(g, u); });
+    auto ok = [&](uint32_t u) { return type_ok(g, u, type); };
+    const unsigned long long base = reserve_block(o, i, scan_count(bm, bm_words, ok), &s_cnt, &s_base);
+    scan_write(bm, bm_words, base, o.out, ok, &s_pos);
+}
+
+__global__ __launch_bounds__(64) void lookup_depth_page_tier1_kernel(Rows g, const uint32_t *targets,
+                                                                     const uint32_t *max_depth, const uint32_t *from,
+                                                                     uint32_t n, uint32_t type, int force_tier2,
+                                                                     paged::PageOut o, unsigned long long *frontier,
+                                                                     uint32_t *ovf_list, unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = targets[i];
+    if (t >= g.N) {  // NONE: the empty page; any other id outside the snapshot: INVALID
+        if (lane == 0) paged::page_invalid(o, i, t != KETOGPU_NODE_NONE);
+        return;
+    }
+    uint32_t fr = 0;
+    if (force_tier2 || !depth::tier1_closure(g, g.Nx, t, depth::limit_of(max_depth, i), lane, set, work, fr,
+                                              [&](uint32_t u) { return any_type(g, u); })) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    if (lane == 0 && fr) frontier[i] = fr;
+    paged::page_finish_wave(set, kSlotsLds, lane, i, from[i], o, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
+__global__ __launch_bounds__(kT2Block) void lookup_depth_page_tier2_kernel(
+    Rows g, const uint32_t *targets, const uint32_t *max_depth, const uint32_t *from, uint32_t type, paged::PageOut o,
+    unsigned long long *frontier, const uint32_t *ovf_list, uint32_t first, uint32_t *bitmaps, uint64_t bm_words,
+    uint32_t *worklists) {
+    __shared__ unsigned int s_tail, s_cnt, s_rem, s_fr;
+    __shared__ uint32_t s_wave[kT2Block / 64];
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const uint32_t t = targets[i];
+    uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
+    uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
+    if (threadIdx.x == 0) s_tail = 0, s_cnt = 0, s_rem = 0, s_fr = 0;
+    __syncthreads();
+    if (t >= g.N) return;  // (tier 1 lists valid targets only)
+    depth::LevelStop stop(&s_tail, depth::limit_of(max_depth, i));
+    tier2_closure(g, g.Nx, t, bm, wl, &s_tail, [](uint32_t, uint32_t) {}, depth::LevelStopRef{&stop});
+    depth::tier2_frontier(stop, wl, frontier + i, &s_fr, [&](uint32_t u) { return any_type(g, u); });
+    const uint32_t lo = from[i];
+    auto ok = [&](uint32_t u) { return type_ok(g, u, type); };
+    paged::page_select_block(bm, bm_words, lo, o.limit, o.out + (uint64_t)i * o.limit, s_wave, ok);
+    __syncthreads();  // the selection has read the bitmap
+    page_report(o, i, page_count_clear(bm, bm_words, lo, ok), &s_cnt, &s_rem);
+}
+
 }  // namespace
 
 struct ketogpu_lookup : ListHandle {
@@ -344,6 +454,7 @@ struct ketogpu_lookup : ListHandle {
     ketogpu_lookup_stats st{};
     ketogpu_lookup_path_stats pst{};
     ketogpu_combine_stats cst{};
+    ketogpu_depth_stats dst{};
 
     ketogpu_lookup() : ListHandle("reverse lookup") {}
 
@@ -477,6 +588,47 @@ struct ketogpu_lookup : ListHandle {
             [](Tally &) {});
         cst.last_call_ms = ms_of_call();
     }
+    // ketogpu_lookup_ids_depth: run() with a limit per request (null: none) and the frontier
+    void run_depth(const uint32_t *targets, const uint32_t *max_depth, size_t n, uint32_t type, uint32_t *out,
+                   uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *frontier, uint64_t *needed) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        run_cursor(
+            dst, targets, n, out, capacity, begin, count, needed,
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || targets[i] == NONE; },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_depth_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        (uint32_t)n, type, force_tier2 ? 1 : 0, list_out(capacity), d_front.p, d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return dst.slots = alloc_slots(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(lookup_depth_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_depth, type,
+                        list_out(capacity), d_front.p, d_ovf.p, first, d_bm.p, bm_words, d_wl.p);
+            });
+        dst.cut_requests += read_frontier(frontier, n);
+        dst.last_call_ms = ms_of_call();
+    }
+
+    // ketogpu_lookup_page_depth: run_page() with a limit per request and the frontier
+    void run_page_depth(const uint32_t *targets, const uint32_t *max_depth, const uint32_t *from, size_t n,
+                        uint32_t type, uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count,
+                        uint64_t *remaining, uint64_t *frontier) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        ListHandle::run_page(
+            dst, targets, from, n, limit, out, returned, count, remaining,
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_depth_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        d_from.p, (uint32_t)n, type, force_tier2 ? 1 : 0, page_out(limit), d_front.p, d_ovf.p,
+                        ovf_count);
+            },
+            [&](uint32_t ovf) { return dst.slots = alloc_slots(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(lookup_depth_page_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_depth,
+                        d_from.p, type, page_out(limit), d_front.p, d_ovf.p, first, d_bm.p, bm_words, d_wl.p);
+            },
+            [](Tally &) {});
+        dst.cut_requests += read_frontier(frontier, n);
+        dst.last_call_ms = ms_of_call();
+    }
 };
 
 extern "C" {
@@ -532,6 +684,25 @@ int ketogpu_lookup_combine_page(ketogpu_lookup *l, const uint32_t *a, const uint
     if (l && op > KETOGPU_COMBINE_OR) return einval(l->what + ": an unknown combine operator");
     return list_call(l, n && (!a || !b || !out || !returned || !count || !remaining), n, "pairs", &limit, [&] {
         l->run_combine_page(a, b, from, n, op, type, limit, out, returned, count, remaining);
+    });
+}
+
+int ketogpu_lookup_depth_stats_get(const ketogpu_lookup *l, ketogpu_depth_stats *out) {
+    return list_stats_get(l, &ketogpu_lookup::dst, out);
+}
+
+int ketogpu_lookup_ids_depth(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth, size_t n,
+                             uint32_t type, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                             uint64_t *frontier, uint64_t *needed) {
+    return list_call(l, !needed || (n && (!targets || !begin || !count)) || (capacity && !out), n, "targets", nullptr,
+                     [&] { l->run_depth(targets, max_depth, n, type, out, capacity, begin, count, frontier, needed); });
+}
+
+int ketogpu_lookup_page_depth(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth,
+                              const uint32_t *from, size_t n, uint32_t type, uint32_t limit, uint32_t *out,
+                              uint32_t *returned, uint64_t *count, uint64_t *remaining, uint64_t *frontier) {
+    return list_call(l, n && (!targets || !out || !returned || !count || !remaining), n, "targets", &limit, [&] {
+        l->run_page_depth(targets, max_depth, from, n, type, limit, out, returned, count, remaining, frontier);
     });
 }
 

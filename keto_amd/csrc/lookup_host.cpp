@@ -132,6 +132,70 @@ int ketogpu_snapshot_lookup(const ketogpu_snapshot *sp, uint32_t target, uint32_
     }
 }
 
+// ketogpu_snapshot_lookup level by level (DESIGN.md "Depth-limited listings"): the worklist is
+// first in, first out, so its entries come in levels; the search stops before a row of level
+// max_depth is read, and what is then left on the worklist is that level's interior members.
+int ketogpu_snapshot_lookup_depth(const ketogpu_snapshot *sp, uint32_t target, uint32_t type, uint32_t max_depth,
+                                  uint32_t **ids, uint64_t *n, uint64_t *frontier) {
+    if (!sp || !ids || !n) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *ids = nullptr;
+    *n = 0;
+    if (frontier) *frontier = 0;
+    try {
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        std::shared_lock<std::shared_mutex> rd(s.mu);
+        if (s.has_ambiguous)
+            throw Error(KETOGPU_EINVAL, "reverse lookup: the snapshot has shared Subject.String() keys (R4)");
+        if (target != NONE && target >= s.N) throw Error(KETOGPU_EINVAL, "target outside the snapshot");
+        std::vector<uint32_t> res;
+        if (target != NONE) {
+            auto types = type_index_of(s);
+            std::unordered_set<uint32_t> seen;
+            std::vector<uint32_t> work;
+            auto row = [&](uint32_t v) {
+                for (uint64_t j = s.rev_off[v]; j < s.rev_off[v + 1]; j++) {
+                    const uint32_t u = s.rev_col[j];
+                    if (!seen.insert(u).second) continue;
+                    if (u < s.Ni) work.push_back(u);
+                    if (u < s.Nx && type_matches(types->node_type[u], type)) res.push_back(u);
+                }
+            };
+            row(target);
+            size_t head = 0, level_end = 0;  // the row at hand is of `level`, which ends at work[level_end)
+            for (uint32_t level = 0;;) {
+                if (head == level_end) {  // work[head ..) is the next level
+                    level++;
+                    level_end = work.size();
+                    if (head == work.size()) break;
+                    if (level == max_depth) {  // (a placeholder is interior, but no member)
+                        uint64_t fr = 0;
+                        for (size_t k = head; k < work.size(); k++) fr += types->node_type[work[k]] != KETOGPU_TYPE_NONE;
+                        if (frontier) *frontier = fr;
+                        break;
+                    }
+                }
+                row(work[head++]);
+            }
+            std::sort(res.begin(), res.end());
+        }
+        uint32_t *p = (uint32_t *)malloc(std::max<size_t>(res.size(), 1) * sizeof(uint32_t));
+        if (!p) throw std::bad_alloc();
+        if (!res.empty()) memcpy(p, res.data(), res.size() * sizeof(uint32_t));
+        *ids = p;
+        *n = res.size();
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
+
 // A breadth-first search from the target over the reverse rows: rows are expanded in the order
 // their nodes were first seen, so the first visit of the root lies on a path with the fewest
 // hops.  parent[u] is the node whose row u was first seen in.

@@ -24,11 +24,17 @@
 // finish of paged_finish.hpp instead: the `limit` smallest members >= from[i] to the stride
 // out + i * limit, ascending, with the exact count and what remains; no cursor, no truncation.
 //
+// The depth calls (ketogpu_subjects_ids_depth / _page_depth) list the members within
+// max_depth[i] hops of the root: the full-list and the paged kernels with depth.hpp's level
+// bookkeeping in the closures, both tier-2 finishes, and frontier[i], the interior members the
+// limit left unread, next to the count.
+//
 // Every index is validated before it is used: roots against N, and against Nx before fwd_off
 // is touched; row entries against N before the class array or a bitmap is.
 #include <hip/hip_runtime.h>
 
 #include "combine.hpp"
+#include "depth.hpp"
 #include "hip_host.hpp"
 #include "subjects.hpp"
 
@@ -268,6 +274,176 @@ __global__ __launch_bounds__(kT2Block) void subjects_combine_page_tier2_kernel(
                         s, [&](uint32_t u) { return class_ok(g, u, cls); });
 }
 
+// ---------------------------------------------------------------------- depth-limited listings
+// ketogpu_subjects_ids_depth / _page_depth: the members of subjects(r, C) within max_depth[i]
+// hops of r (DESIGN.md "Depth-limited listings").  The kernels of the plain calls with
+// depth.hpp's closure in tier 1 and its LevelStop in tier 2; both tier-2 finishes are kept: a
+// depth-limited answer is the short list the seen list exists for.  frontier[i] is all zero on
+// entry and is written where a search stopped at its limit.
+
+// a member under any filter: what the frontier counts (a placeholder has no class)
+__device__ inline bool any_class(const Rows &g, uint32_t u) { return class_ok(g, u, KETOGPU_TYPE_ANY); }
+
+// tier2_closure_seen under a depth limit (a sibling: the plain kernels keep theirs), and the
+// frontier of the search to *frontier.  *s_fr is an LDS counter, zero on entry.
+__device__ __forceinline__ void tier2_closure_seen_depth(const Rows &g, uint32_t r, uint32_t max_depth, uint32_t *bm,
+                                                         uint32_t *wl, uint32_t *seen, uint32_t list_cap,
+                                                         unsigned int *s_tail, unsigned int *s_seen,
+                                                         unsigned int *s_fr, unsigned long long *frontier) {
+    depth::LevelStop stop(s_tail, max_depth);
+    tier2_closure(
+        g, g.N, r, bm, wl, s_tail,
+        [&](uint32_t u, uint32_t) {
+            const uint32_t k = atomicAdd(s_seen, 1u);
+            if (k < list_cap) seen[k] = u;
+        },
+        depth::LevelStopRef{&stop});
+    depth::tier2_frontier(stop, wl, frontier, s_fr, [&](uint32_t u) { return any_class(g, u); });
+}
+
+__global__ __launch_bounds__(64) void subjects_depth_tier1_kernel(Rows g, const uint32_t *roots,
+                                                                  const uint32_t *max_depth, uint32_t n, uint32_t cls,
+                                                                  int force_tier2, SOut o,
+                                                                  unsigned long long *frontier, uint32_t *ovf_list,
+                                                                  unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = roots[i];
+    if (r >= g.Nx) {  // NONE and the never-expanded nodes: the empty list; an id outside the snapshot: INVALID
+        if (lane == 0) {
+            o.l.begin[i] = (r < g.N || r == KETOGPU_NODE_NONE) ? 0ull : KETOGPU_LOOKUP_INVALID;
+            o.l.count[i] = 0;
+        }
+        return;
+    }
+    uint32_t fr = 0;
+    if (force_tier2 || !depth::tier1_closure(g, g.N, r, depth::limit_of(max_depth, i), lane, set, work, fr,
+                                              [&](uint32_t u) { return any_class(g, u); })) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    if (lane == 0 && fr) frontier[i] = fr;
+    tier1_finish(set, lane, i, o.l, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
+__global__ __launch_bounds__(kT2Block) void subjects_depth_tier2_kernel(Rows g, const uint32_t *roots,
+                                                                        const uint32_t *max_depth, uint32_t cls,
+                                                                        SOut o, unsigned long long *frontier,
+                                                                        const uint32_t *ovf_list, uint32_t first,
+                                                                        uint32_t *bitmaps, uint64_t bm_words,
+                                                                        uint32_t *worklists, uint32_t *seen_lists,
+                                                                        uint32_t list_cap) {
+    __shared__ unsigned int s_tail, s_seen, s_cnt, s_pos, s_fr;
+    __shared__ unsigned long long s_base;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const uint32_t r = roots[i];
+    uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
+    uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
+    uint32_t *seen = seen_lists + (uint64_t)blockIdx.x * list_cap;
+    const unsigned tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) s_tail = 0, s_seen = 0, s_cnt = 0, s_pos = 0, s_fr = 0;
+    __syncthreads();
+    if (r >= g.Nx) return;  // (tier 1 lists expandable roots only)
+    tier2_closure_seen_depth(g, r, depth::limit_of(max_depth, i), bm, wl, seen, list_cap, &s_tail, &s_seen, &s_fr,
+                             frontier + i);
+    const uint32_t total = s_seen;
+    const bool by_list = list_cap && total <= list_cap;  // the seen list holds every member within the limit
+    auto ok = [&](uint32_t u) { return class_ok(g, u, cls); };
+    uint32_t c = 0;  // count the members of the class
+    if (by_list) {
+        for (uint32_t k = tid; k < total; k += kT2Block) {
+            const uint32_t u = seen[k];
+            c += ok(u);
+            bm[u >> 5] = 0;  // every set bit of the word is some member's: all of them store the same zero
+        }
+    } else {
+        c = scan_count(bm, bm_words, ok);
+    }
+    const unsigned long long base = reserve_block(o.l, i, c, &s_cnt, &s_base);
+    if (tid == 0) atomicAdd(by_list ? o.list_finishes : o.scan_finishes, 1ull);
+    if (!by_list) {
+        scan_write(bm, bm_words, base, o.l.out, ok, &s_pos);
+        return;
+    }
+    if (base == KETOGPU_LOOKUP_TRUNCATED) return;
+    for (uint32_t k0 = 0; k0 < total; k0 += kT2Block) {  // (a uniform trip count: the ballot sees whole waves)
+        const uint32_t k = k0 + tid;
+        const uint32_t u = k < total ? seen[k] : kEmpty;
+        const bool m = ok(u);
+        const unsigned long long mm = __ballot(m);
+        uint32_t p = 0;
+        if (lane == 0 && mm) p = atomicAdd(&s_pos, (unsigned)__popcll(mm));
+        p = __shfl(p, 0);
+        if (m) o.l.out[base + p + __popcll(mm & ((1ull << lane) - 1))] = u;
+    }
+}
+
+__global__ __launch_bounds__(64) void subjects_depth_page_tier1_kernel(Rows g, const uint32_t *roots,
+                                                                       const uint32_t *max_depth, const uint32_t *from,
+                                                                       uint32_t n, uint32_t cls, int force_tier2,
+                                                                       paged::PageOut o, unsigned long long *frontier,
+                                                                       uint32_t *ovf_list, unsigned int *ovf_count) {
+    __shared__ uint32_t set[kSlotsLds];
+    __shared__ uint32_t work[kSetCap + 64];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = roots[i];
+    if (r >= g.Nx) {  // NONE and the never-expanded nodes: the empty page; an id outside the snapshot: INVALID
+        if (lane == 0) paged::page_invalid(o, i, !(r < g.N || r == KETOGPU_NODE_NONE));
+        return;
+    }
+    uint32_t fr = 0;
+    if (force_tier2 || !depth::tier1_closure(g, g.N, r, depth::limit_of(max_depth, i), lane, set, work, fr,
+                                              [&](uint32_t u) { return any_class(g, u); })) {
+        if (lane == 0) ovf_list[atomicAdd(ovf_count, 1u)] = i;
+        return;
+    }
+    if (lane == 0 && fr) frontier[i] = fr;
+    paged::page_finish_wave(set, kSlotsLds, lane, i, from[i], o, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
+__global__ __launch_bounds__(kT2Block) void subjects_depth_page_tier2_kernel(
+    Rows g, const uint32_t *roots, const uint32_t *max_depth, const uint32_t *from, uint32_t cls, paged::PageOut o,
+    unsigned long long *frontier, unsigned long long *list_finishes, unsigned long long *scan_finishes,
+    const uint32_t *ovf_list, uint32_t first, uint32_t *bitmaps, uint64_t bm_words, uint32_t *worklists,
+    uint32_t *seen_lists, uint32_t list_cap) {
+    __shared__ unsigned int s_tail, s_seen, s_cnt, s_rem, s_fr;
+    __shared__ uint32_t s_wave[kT2Block / 64];
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const uint32_t r = roots[i];
+    uint32_t *bm = bitmaps + (uint64_t)blockIdx.x * bm_words;
+    uint32_t *wl = worklists + (uint64_t)blockIdx.x * g.Ni;
+    uint32_t *seen = seen_lists + (uint64_t)blockIdx.x * list_cap;
+    const unsigned tid = threadIdx.x;
+    if (tid == 0) s_tail = 0, s_seen = 0, s_cnt = 0, s_rem = 0, s_fr = 0;
+    __syncthreads();
+    if (r >= g.Nx) return;  // (tier 1 lists expandable roots only)
+    tier2_closure_seen_depth(g, r, depth::limit_of(max_depth, i), bm, wl, seen, list_cap, &s_tail, &s_seen, &s_fr,
+                             frontier + i);
+    const uint32_t total = s_seen;
+    const bool by_list = list_cap && total <= list_cap;  // the seen list holds every member within the limit
+    const uint32_t lo = from[i];
+    auto ok = [&](uint32_t u) { return class_ok(g, u, cls); };
+    paged::page_select_block(bm, bm_words, lo, o.limit, o.out + (uint64_t)i * o.limit, s_wave, ok);
+    __syncthreads();  // the selection has read the bitmap
+    PageCount mine{0, 0};
+    if (by_list) {
+        for (uint32_t k = tid; k < total; k += kT2Block) {
+            const uint32_t u = seen[k];
+            const bool m = ok(u);
+            mine.count += m;
+            mine.remaining += m && u >= lo;
+            bm[u >> 5] = 0;  // every set bit of the word is some member's: all of them store the same zero
+        }
+    } else {
+        mine = page_count_clear(bm, bm_words, lo, ok);
+    }
+    page_report(o, i, mine, &s_cnt, &s_rem);
+    if (tid == 0) atomicAdd(by_list ? list_finishes : scan_finishes, 1ull);
+}
+
 }  // namespace
 
 struct ketogpu_subjects : ListHandle {
@@ -276,6 +452,7 @@ struct ketogpu_subjects : ListHandle {
     std::vector<uint32_t> h_col;
     ketogpu_subjects_stats st{};
     ketogpu_combine_stats cst{};
+    ketogpu_depth_stats dst{};
 
     ketogpu_subjects() : ListHandle("subject listing") {}
 
@@ -389,6 +566,58 @@ struct ketogpu_subjects : ListHandle {
         cst.last_call_ms = ms_of_call();
     }
 
+    // ketogpu_subjects_ids_depth: run() with a limit per request (null: none) and the frontier
+    void run_depth(const uint32_t *roots, const uint32_t *max_depth, size_t n, uint32_t cls, uint32_t *out,
+                   uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *frontier, uint64_t *needed) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        count_depth_finishes(
+            run_cursor(
+                dst, roots, n, out, capacity, begin, count, needed,
+                [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || roots[i] == NONE; },
+                [&](unsigned int *ovf_count) {
+                    KLAUNCH(subjects_depth_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                            (uint32_t)n, cls, force_tier2 ? 1 : 0, subjects_out(capacity), d_front.p, d_ovf.p,
+                            ovf_count);
+                },
+                [&](uint32_t ovf) { return dst.slots = alloc_slots(ovf); },
+                [&](uint32_t first, uint32_t k) {
+                    KLAUNCH(subjects_depth_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_depth, cls,
+                            subjects_out(capacity), d_front.p, d_ovf.p, first, d_bm.p, bm_words, d_wl.p, d_aux.p,
+                            list_cap);
+                }),
+            frontier, n);
+    }
+
+    // ketogpu_subjects_page_depth: run_page() with a limit per request and the frontier
+    void run_page_depth(const uint32_t *roots, const uint32_t *max_depth, const uint32_t *from, size_t n, uint32_t cls,
+                        uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count, uint64_t *remaining,
+                        uint64_t *frontier) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        count_depth_finishes(
+            ListHandle::run_page(
+                dst, roots, from, n, limit, out, returned, count, remaining,
+                [&](unsigned int *ovf_count) {
+                    KLAUNCH(subjects_depth_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p,
+                            d_depth, d_from.p, (uint32_t)n, cls, force_tier2 ? 1 : 0, page_out(limit), d_front.p,
+                            d_ovf.p, ovf_count);
+                },
+                [&](uint32_t ovf) { return dst.slots = alloc_slots(ovf); },
+                [&](uint32_t first, uint32_t k) {
+                    KLAUNCH(subjects_depth_page_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_depth,
+                            d_from.p, cls, page_out(limit), d_front.p, d_ctr.p + 3, d_ctr.p + 4, d_ovf.p, first,
+                            d_bm.p, bm_words, d_wl.p, d_aux.p, list_cap);
+                },
+                [&](Tally &t) { read_ctrs(t); }),  // (the finish counters)
+            frontier, n);
+    }
+
+    void count_depth_finishes(const Tally &t, uint64_t *frontier, size_t n) {
+        dst.list_finishes += t.ctr[3];
+        dst.scan_finishes += t.ctr[4];
+        dst.cut_requests += read_frontier(frontier, n);
+        dst.last_call_ms = ms_of_call();
+    }
+
     void count_finishes(const Tally &t) {
         st.list_finishes += t.ctr[3];
         st.scan_finishes += t.ctr[4];
@@ -443,6 +672,25 @@ int ketogpu_subjects_combine_page(ketogpu_subjects *h, const uint32_t *a, const 
     if (h && op > KETOGPU_COMBINE_OR) return einval(h->what + ": an unknown combine operator");
     return list_call(h, n && (!a || !b || !out || !returned || !count || !remaining), n, "pairs", &limit, [&] {
         h->run_combine_page(a, b, from, n, op, cls, limit, out, returned, count, remaining);
+    });
+}
+
+int ketogpu_subjects_depth_stats_get(const ketogpu_subjects *h, ketogpu_depth_stats *out) {
+    return list_stats_get(h, &ketogpu_subjects::dst, out);
+}
+
+int ketogpu_subjects_ids_depth(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth, size_t n,
+                               uint32_t cls, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                               uint64_t *frontier, uint64_t *needed) {
+    return list_call(h, !needed || (n && (!roots || !begin || !count)) || (capacity && !out), n, "roots", nullptr,
+                     [&] { h->run_depth(roots, max_depth, n, cls, out, capacity, begin, count, frontier, needed); });
+}
+
+int ketogpu_subjects_page_depth(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth,
+                                const uint32_t *from, size_t n, uint32_t cls, uint32_t limit, uint32_t *out,
+                                uint32_t *returned, uint64_t *count, uint64_t *remaining, uint64_t *frontier) {
+    return list_call(h, n && (!roots || !out || !returned || !count || !remaining), n, "roots", &limit, [&] {
+        h->run_page_depth(roots, max_depth, from, n, cls, limit, out, returned, count, remaining, frontier);
     });
 }
 

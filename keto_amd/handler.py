@@ -10,6 +10,8 @@ caller gets the reference's responses from the new engines:
     POST /check/batch  (new, SURVEY.md 8(f) row 2)    200 {"results": [{"allowed": bool} | {"error": ...}]}
     GET  /list/objects   (new, DESIGN.md "Sorted, paged lists")  200 {"objects": [...], "next_page_token", "total"}
     GET  /list/subjects  (new, same section)                     200 {"subjects": [...], "next_page_token", "total"}
+         both take max-depth (Keto's spelling; DESIGN.md "Depth-limited listings"): a positive integer, else 400;
+         the list within that many hops, and the body gains "complete": true | false
     GET  /list/objects/combined, /list/subjects/combined  (new, DESIGN.md "Combined listings")  the same bodies for
          the list of two subjects / two objects under op = and | andnot | or
     GET  /check/explain  (new, DESIGN.md "Explain")  200 {"allowed":true,"path":[...]} | 403 {"allowed":false,"path":[]}
@@ -261,6 +263,21 @@ class Handler:
             raise BadRequest(f"page_size {size} is outside [1, {_lib.PAGE_LIMIT_MAX}]")
         return size, _get(q, "page_token") or ""
 
+    @staticmethod
+    def _max_depth(q):
+        """max-depth -> None when the parameter is absent, else a positive integer that fits the
+        library's uint32 (parsed as Go parses an int); anything else is a BadRequest"""
+        if "max-depth" not in q:
+            return None
+        raw = _get(q, "max-depth")
+        try:
+            depth = go_parse_int(raw)
+        except ValueError as e:
+            raise BadRequest(f"strconv.ParseInt: parsing {json.dumps(raw or '')}: {e}")
+        if depth < 1:
+            raise BadRequest(f"max-depth {depth} is not a positive integer")
+        return min(depth, 0xFFFFFFFF)  # (every depth beyond any closure's acts the same)
+
     def _list(self, backend, query, call):
         if backend is None:
             return self._error(404, "this server has no list handle")
@@ -277,25 +294,38 @@ class Handler:
 
     def get_list_objects(self, query):
         """namespace, relation, subject_id | subject_set.*, page_size, page_token -> the objects o
-        with Check(namespace:o#relation@subject)"""
+        with Check(namespace:o#relation@subject); with max-depth, those within that many hops
+        of the subject, and "complete" """
         def call(q, size, token):
+            depth = self._max_depth(q)
             t = tuple_from_url(q)  # the subject is required
+            if depth is not None:
+                items, nxt, total, complete = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size,
+                                                                            token, max_depth=depth)
+                return {"objects": items, "next_page_token": nxt, "total": total, "complete": bool(complete)}
             items, nxt, total = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size, token)
             return {"objects": items, "next_page_token": nxt, "total": total}
         return self._list(self.lookup, query, call)
 
     def get_list_subjects(self, query):
         """namespace, object, relation, kind (ids | any | ns#relation), page_size, page_token -> the
-        subjects s with Check(namespace:object#relation@s), in the JSON form check requests use"""
+        subjects s with Check(namespace:object#relation@s), in the JSON form check requests use;
+        with max-depth, those within that many hops of the object, and "complete" """
         def call(q, size, token):
+            depth = self._max_depth(q)
             kind = _get(q, "kind") or "ids"
             if kind not in ("ids", "any"):
                 ns, sep, rel = kind.partition("#")
                 if not sep:
                     raise BadRequest(f'kind {kind!r}: expected "ids", "any" or "namespace#relation"')
                 kind = (ns, rel)
-            items, nxt, total = self.subjects.list_subjects_page(
-                _get(q, "namespace") or "", _get(q, "object") or "", _get(q, "relation") or "", kind, size, token)
+            root = (_get(q, "namespace") or "", _get(q, "object") or "", _get(q, "relation") or "")
+            if depth is not None:
+                items, nxt, total, complete = self.subjects.list_subjects_page(*root, kind, size, token,
+                                                                               max_depth=depth)
+                return {"subjects": [s.to_dict() for s in items], "next_page_token": nxt, "total": total,
+                        "complete": bool(complete)}
+            items, nxt, total = self.subjects.list_subjects_page(*root, kind, size, token)
             return {"subjects": [s.to_dict() for s in items], "next_page_token": nxt, "total": total}
         return self._list(self.subjects, query, call)
 

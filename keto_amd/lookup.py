@@ -27,6 +27,13 @@ does not — come from one call as well (ketogpu_lookup_combine / ketogpu_subjec
 _page forms, DESIGN.md "Combined listings"): `combine_ids`, `combine_page_raw`,
 `ListObjectsCombined` / `ListSubjectsCombined` with op "and" | "andnot" | "or", on the device
 handles and, as numpy set algebra over the host lists, on the CPU twins.
+
+A listing also comes cut at a number of hops — who holds this document directly, who through one
+group (ketogpu_*_ids_depth / ketogpu_*_page_depth, DESIGN.md "Depth-limited listings"):
+`lookup_depth` / `subject_depth` and their `_raw` and `_page_raw` forms take one `max_depth` per
+request (DEPTH_ALL: no limit) and also return `frontier`, the interior members at exactly that
+distance; `list_*_depth_batch` return names and `complete`, and the named calls take a keyword
+`max_depth`.  `host_lookup_depth` / `host_subjects_depth` are the level-by-level CPU twins.
 """
 import ctypes as C
 
@@ -40,6 +47,7 @@ TYPE_ANY, TYPE_NONE = L.TYPE_ANY, L.TYPE_NONE
 TRUNCATED, INVALID = L.LOOKUP_TRUNCATED, L.LOOKUP_INVALID
 CLASS_SUBJECT_ID, CLASS_UNTYPED_SET = L.CLASS_SUBJECT_ID, L.CLASS_UNTYPED_SET
 PAGE_LIMIT_MAX, PAGE_INVALID = L.PAGE_LIMIT_MAX, L.PAGE_INVALID
+DEPTH_ALL = L.DEPTH_ALL
 
 
 # ---- pages: tokens and sizes, shared by the device handles and their CPU twins
@@ -111,9 +119,12 @@ def _page_args(ids, from_ids, limit):
 class _ObjectPages:
     """list_objects_page over self.lookup_page_raw and self.snapshot"""
 
-    def list_objects_page_batch(self, namespace, relation, requests, page_size=100):
+    def list_objects_page_batch(self, namespace, relation, requests, page_size=100, max_depth=None):
         """requests: (subject, page_token) pairs, one device call for all of them -> per
-        request (object names in node-id order, next_page_token, total)"""
+        request (object names in node-id order, next_page_token, total).  max_depth (one number,
+        or one per request): the objects within that many hops, and a fourth element `complete`"""
+        if max_depth is not None:
+            return self._list_objects_page_depth(namespace, relation, list(requests), page_size, max_depth)
         page_size = check_page_size(page_size)
         requests = list(requests)
         lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
@@ -129,18 +140,39 @@ class _ObjectPages:
             res.append((names, next_page_token(out[i], k, remaining[i]), int(count[i])))
         return res
 
-    def list_objects_page(self, namespace, relation, subject, page_size=100, page_token=""):
+    def list_objects_page(self, namespace, relation, subject, page_size=100, page_token="", max_depth=None):
         """-> (items, next_page_token, total): at most page_size object names o with
-        Check(namespace:o#relation@subject), in node-id order from the token on"""
-        return self.list_objects_page_batch(namespace, relation, [(subject, page_token)], page_size)[0]
+        Check(namespace:o#relation@subject), in node-id order from the token on.  With max_depth:
+        of the objects within that many hops, -> (items, next_page_token, total, complete)"""
+        return self.list_objects_page_batch(namespace, relation, [(subject, page_token)], page_size, max_depth)[0]
+
+    def _list_objects_page_depth(self, namespace, relation, requests, page_size, max_depth):
+        page_size = check_page_size(page_size)
+        lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
+        depth = depth_array(max_depth, len(requests))
+        ty = self.snapshot.type_id(namespace, relation)
+        targets = resolve_subjects(self.snapshot, [s for s, _ in requests])
+        if ty == TYPE_NONE:
+            return [([], "", 0, True) for _ in requests]
+        out, returned, count, remaining, frontier = self.lookup_depth_page_raw(targets, depth, lo, ty, page_size)
+        res = []
+        for i in range(len(requests)):
+            k = int(returned[i])
+            names = [self.snapshot.node_info(int(v))["id"] for v in out[i, :k]]
+            res.append((names, next_page_token(out[i], k, remaining[i]), int(count[i]), not frontier[i]))
+        return res
 
 
 class _SubjectPages:
     """list_subjects_page over self.subject_page_raw and self.snapshot"""
 
-    def list_subjects_page_batch(self, requests, kind="ids", page_size=100):
+    def list_subjects_page_batch(self, requests, kind="ids", page_size=100, max_depth=None):
         """requests: ((namespace, object, relation), page_token) pairs, one device call for all
-        of them -> per request (SubjectID / SubjectSet in node-id order, next_page_token, total)"""
+        of them -> per request (SubjectID / SubjectSet in node-id order, next_page_token, total).
+        max_depth (one number, or one per request): the subjects within that many hops, and a
+        fourth element `complete`"""
+        if max_depth is not None:
+            return self._list_subjects_page_depth(list(requests), kind, page_size, max_depth)
         page_size = check_page_size(page_size)
         requests = list(requests)
         lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
@@ -156,10 +188,159 @@ class _SubjectPages:
             res.append((subs, next_page_token(out[i], k, remaining[i]), int(count[i])))
         return res
 
-    def list_subjects_page(self, namespace, object, relation, kind="ids", page_size=100, page_token=""):
+    def list_subjects_page(self, namespace, object, relation, kind="ids", page_size=100, page_token="",
+                           max_depth=None):
         """-> (items, next_page_token, total): at most page_size subjects s with
-        Check(namespace:object#relation@s), in node-id order from the token on"""
-        return self.list_subjects_page_batch([((namespace, object, relation), page_token)], kind, page_size)[0]
+        Check(namespace:object#relation@s), in node-id order from the token on.  With max_depth:
+        of the subjects within that many hops, -> (items, next_page_token, total, complete)"""
+        return self.list_subjects_page_batch([((namespace, object, relation), page_token)], kind, page_size,
+                                             max_depth)[0]
+
+    def _list_subjects_page_depth(self, requests, kind, page_size, max_depth):
+        page_size = check_page_size(page_size)
+        lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
+        depth = depth_array(max_depth, len(requests))
+        cls = _class_of_kind(self.snapshot, kind)
+        roots = resolve_roots(self.snapshot, [tuple(r) for r, _ in requests])
+        if cls == TYPE_NONE:
+            return [([], "", 0, True) for _ in requests]
+        out, returned, count, remaining, frontier = self.subject_depth_page_raw(roots, depth, lo, cls, page_size)
+        res = []
+        for i in range(len(requests)):
+            k = int(returned[i])
+            subs = [self.snapshot.describe(int(v)) for v in out[i, :k]]
+            res.append((subs, next_page_token(out[i], k, remaining[i]), int(count[i]), not frontier[i]))
+        return res
+
+
+# ---- depth-limited listings (include/ketogpu.h "depth-limited listings", DESIGN.md
+# "Depth-limited listings"), shared by the device handles and their CPU twins
+def depth_array(max_depth, n):
+    """one limit for every request, or one per request -> uint32[n]; None -> None (no limit for
+    any request).  DEPTH_ALL (0) is no limit; a limit that is no integer in [0, 2^32) raises
+    KetoError(EINVAL)"""
+    if max_depth is None:
+        return None
+    try:
+        d = np.asarray(max_depth)
+        if d.dtype == bool or not np.issubdtype(d.dtype, np.integer):
+            raise ValueError
+        d = np.broadcast_to(d, (n,)) if d.ndim == 0 else d
+        if d.shape != (n,) or (n and (d.min() < 0 or d.max() > 0xFFFFFFFF)):
+            raise ValueError
+    except (ValueError, TypeError):
+        raise L.KetoError(L.EINVAL, f"max_depth {max_depth!r}: expected one integer in [0, 2^32) for all requests "
+                                    "or one per request") from None
+    return np.ascontiguousarray(d, dtype=np.uint32)
+
+
+def _depth_lists(raw, ids, max_depth, cap, invalid):
+    """_all_lists over a depth call raw(ids, depth, cap) -> (out, begin, count, frontier, needed)
+    -> (ascending lists, frontier).  The frontier of a request does not depend on the capacity."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    depth = depth_array(max_depth, len(ids))
+    frontier = np.zeros(len(ids), dtype=np.uint64)
+
+    def call(idx, c):
+        out, begin, count, fr, needed = raw(ids[idx], None if depth is None else depth[idx], c)
+        frontier[idx] = fr
+        return out, begin, count, needed
+    lists = _all_lists(call, len(ids), 64 * len(ids) if cap is None else int(cap), True,
+                       lambda k: f"id {int(ids[k])} is outside the snapshot")
+    return lists, frontier
+
+
+def _host_cursor(lists, capacity):
+    """(out, begin, count, needed) as a cursor call lays its lists out (None: INVALID)"""
+    n = len(lists)
+    out = np.zeros(int(capacity), dtype=np.uint32)
+    begin, count = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    cursor = 0
+    for i, ids in enumerate(lists):
+        if ids is None:
+            begin[i] = INVALID
+            continue
+        count[i] = len(ids)
+        if cursor + len(ids) <= capacity:
+            out[cursor:cursor + len(ids)] = ids
+            begin[i] = cursor
+        else:
+            begin[i] = TRUNCATED
+        cursor += len(ids)  # every list reserves, written or not
+    return out, begin, count, cursor
+
+
+class _HostDepth:
+    """the depth calls of a CPU twin over self._depth_members(x, k, filter_id) -> (ascending ids,
+    frontier), laid out as the device calls lay their results out"""
+
+    def _depth_all(self, ids, max_depth, filter_id):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        depth = depth_array(max_depth, len(ids))
+        n_nodes = self.snapshot.stats()["num_nodes"]
+        lists, frontier = [], np.zeros(len(ids), dtype=np.uint64)
+        for i, x in enumerate(ids):
+            if x >= n_nodes and x != L.NODE_NONE:
+                lists.append(None)
+                continue
+            m, frontier[i] = self._depth_members(int(x), DEPTH_ALL if depth is None else int(depth[i]), filter_id)
+            lists.append(m)
+        return lists, frontier
+
+    def _ids_depth_raw(self, ids, max_depth, filter_id=TYPE_ANY, capacity=0):
+        lists, frontier = self._depth_all(ids, max_depth, filter_id)
+        out, begin, count, needed = _host_cursor(lists, capacity)
+        return out, begin, count, frontier, needed
+
+    def _page_depth_raw(self, ids, max_depth, from_ids=None, filter_id=TYPE_ANY, limit=100):
+        lists, frontier = self._depth_all(ids, max_depth, filter_id)
+        return _host_pages(lists, [m is None for m in lists], from_ids, limit) + (frontier,)
+
+
+class _ObjectsDepth:
+    """the depth-limited object lists over self.lookup_depth_raw and self.snapshot"""
+
+    def lookup_depth(self, targets, max_depth, type_id=TYPE_ANY, capacity=None):
+        """-> (one ascending uint32 array per target, frontier): lookup_ids within max_depth hops
+        (one number, or one per target; DEPTH_ALL: no limit), with lookup_ids' re-issue of
+        truncated lists.  frontier[i] == 0: list i is the whole closure."""
+        return _depth_lists(lambda t, d, c: self.lookup_depth_raw(t, d, type_id, c), targets, max_depth, capacity,
+                            None)
+
+    def list_objects_depth_batch(self, namespace, relation, subjects, max_depth):
+        """per subject: the sorted object names o with Check(namespace:o#relation@subject) that
+        are within max_depth hops of the subject -> (lists, complete); complete[i]: no deeper
+        level was cut off, list i is what list_objects_batch gives"""
+        ty = self.snapshot.type_id(namespace, relation)
+        targets = resolve_subjects(self.snapshot, list(subjects))
+        depth = depth_array(max_depth, len(targets))
+        if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
+            return [[] for _ in targets], [True] * len(targets)
+        lists, frontier = self.lookup_depth(targets, depth, ty)
+        return ([sorted(self.snapshot.node_info(int(v))["id"] for v in ids) for ids in lists],
+                [not f for f in frontier])
+
+
+class _SubjectsDepth:
+    """the depth-limited subject lists over self.subject_depth_raw and self.snapshot"""
+
+    def subject_depth(self, roots, max_depth, cls=TYPE_ANY, capacity=None):
+        """-> (one ascending uint32 array per root, frontier): subject_ids within max_depth hops
+        (one number, or one per root; DEPTH_ALL: no limit), with subject_ids' re-issue of
+        truncated lists.  frontier[i] == 0: list i is the whole closure."""
+        return _depth_lists(lambda r, d, c: self.subject_depth_raw(r, d, cls, c), roots, max_depth, capacity, None)
+
+    def list_subjects_depth_batch(self, roots, max_depth, kind="ids"):
+        """per (namespace, object, relation) root: the subjects s with Check(root@s) that are
+        within max_depth hops of the root -> (lists, complete), as list_subjects_batch lists them"""
+        roots = list(roots)
+        cls = _class_of_kind(self.snapshot, kind)
+        ids = resolve_roots(self.snapshot, roots)
+        depth = depth_array(max_depth, len(ids))
+        if cls == TYPE_NONE:
+            return [[] for _ in roots], [True] * len(roots)
+        lists, frontier = self.subject_depth(ids, depth, cls)
+        return [_subjects_of(self.snapshot, v) for v in lists], [not f for f in frontier]
 
 
 # ---- combined listings: M(a) op M(b) (include/ketogpu.h "combined listings", DESIGN.md
@@ -316,11 +497,13 @@ class _HostCombine:
         return _host_pages(lists, [ids is None for ids in lists], from_ids, limit)
 
 
-def _host_ids(snapshot, call, *args):
-    """one ketogpu_snapshot_* call that answers with a malloc'ed id array -> its copy (uint32)"""
+def _host_ids(snapshot, call, *args, frontier=None):
+    """one ketogpu_snapshot_* call that answers with a malloc'ed id array -> its copy (uint32);
+    frontier: a c_uint64 for the trailing output of a depth call"""
     p, n = C.c_void_p(), C.c_uint64()
     lib = snapshot.L
-    L.check(getattr(lib, call)(snapshot.h, *args, C.byref(p), C.byref(n)))
+    tail = () if frontier is None else (C.byref(frontier),)
+    L.check(getattr(lib, call)(snapshot.h, *args, C.byref(p), C.byref(n), *tail))
     try:
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n.value,)).copy() if n.value \
             else np.zeros(0, dtype=np.uint32)
@@ -331,6 +514,17 @@ def _host_ids(snapshot, call, *args):
 def host_lookup(snapshot, target, type_id=TYPE_ANY):
     """ketogpu_snapshot_lookup: ascending node ids (uint32).  No GPU."""
     return _host_ids(snapshot, "ketogpu_snapshot_lookup", int(target), int(type_id))
+
+
+def _host_ids_depth(snapshot, call, x, filter_id, max_depth):
+    """one ketogpu_snapshot_*_depth call -> (ascending ids (uint32), frontier)"""
+    fr = C.c_uint64()
+    return _host_ids(snapshot, call, int(x), int(filter_id), int(max_depth), frontier=fr), fr.value
+
+
+def host_lookup_depth(snapshot, target, max_depth, type_id=TYPE_ANY):
+    """ketogpu_snapshot_lookup_depth: (host_lookup within max_depth hops, frontier).  No GPU."""
+    return _host_ids_depth(snapshot, "ketogpu_snapshot_lookup_depth", target, type_id, max_depth)
 
 
 def resolve_subjects(snapshot, subjects):
@@ -464,6 +658,39 @@ class _Handle:
                                   remaining.ctypes.data))
         return out[:n], returned[:n], count[:n], remaining[:n]
 
+    # ---- depth-limited listings
+    def depth_stats(self):
+        return self._stats(L.DepthStats(), "depth_stats_get")
+
+    def _ids_depth_raw(self, requests, max_depth, filter_id=TYPE_ANY, capacity=0):
+        """one ketogpu_<ABI>_ids_depth call -> (out, begin, count, frontier, needed): _ids_raw's
+        results within max_depth hops (None: no limit; one number for all requests, or one per
+        request), and frontier[i], the interior members at exactly that distance"""
+        requests = np.ascontiguousarray(requests, dtype=np.uint32)
+        n = len(requests)
+        depth = depth_array(max_depth, n)
+        out = np.empty(max(int(capacity), 1), dtype=np.uint32)
+        begin = np.empty(max(n, 1), dtype=np.uint64)
+        count = np.empty(max(n, 1), dtype=np.uint64)
+        frontier = np.zeros(max(n, 1), dtype=np.uint64)
+        needed = C.c_uint64()
+        L.check(self._abi("ids_depth")(self.h, requests.ctypes.data, None if depth is None else depth.ctypes.data, n,
+                                       int(filter_id), out.ctypes.data if capacity else None, int(capacity),
+                                       begin.ctypes.data, count.ctypes.data, frontier.ctypes.data, C.byref(needed)))
+        return out[:int(capacity)], begin[:n], count[:n], frontier[:n], needed.value
+
+    def _page_depth_raw(self, requests, max_depth, from_ids=None, filter_id=TYPE_ANY, limit=100):
+        """one ketogpu_<ABI>_page_depth call -> (out[n, limit], returned, count, remaining,
+        frontier): _page_raw's results within max_depth hops"""
+        requests, lo, n, limit, out, returned, count, remaining = _page_args(requests, from_ids, limit)
+        depth = depth_array(max_depth, n)
+        frontier = np.zeros(max(n, 1), dtype=np.uint64)
+        L.check(self._abi("page_depth")(self.h, requests.ctypes.data, None if depth is None else depth.ctypes.data,
+                                        None if lo is None else lo.ctypes.data, n, int(filter_id), limit,
+                                        out.ctypes.data, returned.ctypes.data, count.ctypes.data,
+                                        remaining.ctypes.data, frontier.ctypes.data))
+        return out[:n], returned[:n], count[:n], remaining[:n], frontier[:n]
+
     # ---- combined listings
     def combine_stats(self):
         return self._stats(L.CombineStats(), "combine_stats_get")
@@ -485,9 +712,17 @@ class _Handle:
         return out[:n], returned[:n], count[:n], remaining[:n]
 
 
-class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined):
+class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth):
     """device handle over a snapshot's reverse rows"""
     ABI, OPTS, STATS = "lookup", L.LookupOpts, L.LookupStats
+
+    def lookup_depth_raw(self, targets, max_depth, type_id=TYPE_ANY, capacity=0):
+        """one ketogpu_lookup_ids_depth call (_ids_depth_raw)"""
+        return self._ids_depth_raw(targets, max_depth, type_id, capacity)
+
+    def lookup_depth_page_raw(self, targets, max_depth, from_ids=None, type_id=TYPE_ANY, limit=100):
+        """one ketogpu_lookup_page_depth call (_page_depth_raw)"""
+        return self._page_depth_raw(targets, max_depth, from_ids, type_id, limit)
 
     def lookup_ids_raw(self, targets, type_id=TYPE_ANY, capacity=0):
         """one ketogpu_lookup_ids call (_ids_raw)"""
@@ -521,16 +756,19 @@ class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined):
     def _objects(self, ids):
         return sorted(self.snapshot.node_info(int(v))["id"] for v in ids)
 
-    def list_objects_batch(self, namespace, relation, subjects):
-        """per subject: the sorted object names o with Check(namespace:o#relation@subject)"""
+    def list_objects_batch(self, namespace, relation, subjects, max_depth=None):
+        """per subject: the sorted object names o with Check(namespace:o#relation@subject); with
+        max_depth, those within that many hops (list_objects_depth_batch's lists)"""
+        if max_depth is not None:
+            return self.list_objects_depth_batch(namespace, relation, subjects, max_depth)[0]
         ty = self.snapshot.type_id(namespace, relation)
         targets = resolve_subjects(self.snapshot, list(subjects))
         if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
             return [[] for _ in targets]
         return [self._objects(ids) for ids in self.lookup_ids(targets, ty)]
 
-    def ListObjects(self, namespace, relation, subject):
-        return self.list_objects_batch(namespace, relation, [subject])[0]
+    def ListObjects(self, namespace, relation, subject, max_depth=None):
+        return self.list_objects_batch(namespace, relation, [subject], max_depth)[0]
 
 
 def host_list_objects(snapshot, namespace, relation, subject):
@@ -542,12 +780,24 @@ def host_list_objects(snapshot, namespace, relation, subject):
     return sorted(snapshot.node_info(int(v))["id"] for v in host_lookup(snapshot, t, ty))
 
 
-class HostLookup(_ObjectPages, _Paths, _HostCombine, _ObjectsCombined):
-    """Lookup's paged, path and combined calls on the CPU: host_lookup's ascending lists, sliced
-    or combined, and host_path's paths laid out as the device call lays them out"""
+class HostLookup(_ObjectPages, _Paths, _HostCombine, _ObjectsCombined, _HostDepth, _ObjectsDepth):
+    """Lookup's paged, path, combined and depth calls on the CPU: host_lookup's ascending lists,
+    sliced or combined, host_path's paths laid out as the device call lays them out, and
+    host_lookup_depth's lists"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def _depth_members(self, x, k, type_id):
+        if x == L.NODE_NONE:
+            return np.zeros(0, dtype=np.uint32), 0
+        return host_lookup_depth(self.snapshot, x, k, type_id)
+
+    def lookup_depth_raw(self, targets, max_depth, type_id=TYPE_ANY, capacity=0):
+        return self._ids_depth_raw(targets, max_depth, type_id, capacity)
+
+    def lookup_depth_page_raw(self, targets, max_depth, from_ids=None, type_id=TYPE_ANY, limit=100):
+        return self._page_depth_raw(targets, max_depth, from_ids, type_id, limit)
 
     def _members(self, x, type_id):
         return self._side(x, type_id, host_lookup)
@@ -591,6 +841,11 @@ def host_subjects(snapshot, root, cls=TYPE_ANY):
     return _host_ids(snapshot, "ketogpu_snapshot_subjects", int(root), int(cls))
 
 
+def host_subjects_depth(snapshot, root, max_depth, cls=TYPE_ANY):
+    """ketogpu_snapshot_subjects_depth: (host_subjects within max_depth hops, frontier).  No GPU."""
+    return _host_ids_depth(snapshot, "ketogpu_snapshot_subjects_depth", root, cls, max_depth)
+
+
 def resolve_roots(snapshot, objects):
     """(namespace, object, relation) triples -> root node ids (NODE_NONE for an unknown
     namespace or a query no tuple matches).  A wildcard query without a snapshot node (a
@@ -627,9 +882,17 @@ def _subjects_of(snapshot, ids):
     return users + sets
 
 
-class Subjects(_Handle, _SubjectPages, _SubjectsCombined):
+class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth):
     """device handle over a snapshot's forward rows"""
     ABI, OPTS, STATS = "subjects", L.SubjectsOpts, L.SubjectsStats
+
+    def subject_depth_raw(self, roots, max_depth, cls=TYPE_ANY, capacity=0):
+        """one ketogpu_subjects_ids_depth call (_ids_depth_raw)"""
+        return self._ids_depth_raw(roots, max_depth, cls, capacity)
+
+    def subject_depth_page_raw(self, roots, max_depth, from_ids=None, cls=TYPE_ANY, limit=100):
+        """one ketogpu_subjects_page_depth call (_page_depth_raw)"""
+        return self._page_depth_raw(roots, max_depth, from_ids, cls, limit)
 
     def subject_ids_raw(self, roots, cls=TYPE_ANY, capacity=0):
         """one ketogpu_subjects_ids call (_ids_raw)"""
@@ -649,10 +912,13 @@ class Subjects(_Handle, _SubjectPages, _SubjectsCombined):
         return self._page_raw(roots, from_ids, cls, limit)
 
     # ---- names
-    def list_subjects_batch(self, roots, kind="ids"):
+    def list_subjects_batch(self, roots, kind="ids", max_depth=None):
         """per (namespace, object, relation) root: the subjects s with Check(root@s), SubjectIDs
         then SubjectSets, each sorted.  kind: "ids" (subject ids only), "any", or a
-        (namespace, relation) pair (subject sets of that type; an unknown pair lists nothing)"""
+        (namespace, relation) pair (subject sets of that type; an unknown pair lists nothing).
+        With max_depth: those within that many hops (list_subjects_depth_batch's lists)"""
+        if max_depth is not None:
+            return self.list_subjects_depth_batch(roots, max_depth, kind)[0]
         roots = list(roots)
         cls = _class_of_kind(self.snapshot, kind)
         ids = resolve_roots(self.snapshot, roots)
@@ -660,16 +926,27 @@ class Subjects(_Handle, _SubjectPages, _SubjectsCombined):
             return [[] for _ in roots]
         return [_subjects_of(self.snapshot, v) for v in self.subject_ids(ids, cls)]
 
-    def ListSubjects(self, namespace, object, relation, kind="ids"):
-        return self.list_subjects_batch([(namespace, object, relation)], kind)[0]
+    def ListSubjects(self, namespace, object, relation, kind="ids", max_depth=None):
+        return self.list_subjects_batch([(namespace, object, relation)], kind, max_depth)[0]
 
 
-class HostSubjects(_SubjectPages, _HostCombine, _SubjectsCombined):
-    """Subjects' paged and combined calls on the CPU: host_subjects' ascending lists, sliced or
-    combined"""
+class HostSubjects(_SubjectPages, _HostCombine, _SubjectsCombined, _HostDepth, _SubjectsDepth):
+    """Subjects' paged, combined and depth calls on the CPU: host_subjects' ascending lists,
+    sliced or combined, and host_subjects_depth's lists"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def _depth_members(self, x, k, cls):
+        if x == L.NODE_NONE:
+            return np.zeros(0, dtype=np.uint32), 0
+        return host_subjects_depth(self.snapshot, x, k, cls)
+
+    def subject_depth_raw(self, roots, max_depth, cls=TYPE_ANY, capacity=0):
+        return self._ids_depth_raw(roots, max_depth, cls, capacity)
+
+    def subject_depth_page_raw(self, roots, max_depth, from_ids=None, cls=TYPE_ANY, limit=100):
+        return self._page_depth_raw(roots, max_depth, from_ids, cls, limit)
 
     def _members(self, x, cls):
         return self._side(x, cls, host_subjects)
@@ -695,4 +972,4 @@ __all__ = ["Lookup", "host_lookup", "host_list_objects", "resolve_subjects", "Su
            "host_list_subjects", "resolve_roots", "TYPE_ANY", "TYPE_NONE", "CLASS_SUBJECT_ID", "CLASS_UNTYPED_SET",
            "TRUNCATED", "INVALID", "SubjectID", "SubjectSet", "HostLookup", "HostSubjects", "PAGE_LIMIT_MAX",
            "PAGE_INVALID", "parse_page_token", "check_page_size", "next_page_token", "host_path", "OP_AND", "OP_ANDNOT",
-           "OP_OR", "op_id"]
+           "OP_OR", "op_id", "DEPTH_ALL", "host_lookup_depth", "host_subjects_depth", "depth_array"]
