@@ -1323,6 +1323,85 @@ int ketogpu_subjects_page_depth(ketogpu_subjects *h, const uint32_t *roots, cons
                                 uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
                                 uint64_t *remaining, uint64_t *frontier);
 
+/* -------------------------------------------------- listings that say why */
+/* Next to every member of a listing, the node whose row grants it and how far from the start it
+ * is: one line per viewer saying through which group and at what distance.  This is the
+ * breadth-first grant tree of a closure, computed by the search that produced the list.
+ *
+ * In the terms of the depth section above (start x, members M_k(x) under the call's type / class
+ * filter, d(x, u) the hop count of ketogpu_snapshot_path), for every listed member u:
+ *
+ *   hops(u) = d(x, u): exact, at least 1, and deterministic.
+ *   via(u)  = a node at distance hops(u) - 1 from x that is joined to u by one edge of the
+ *             closure.  For hops(u) == 1 it is x; otherwise it is an interior member of the
+ *             unfiltered closure.  On the subjects handle u is an entry of row(via): the chain
+ *             reads x -> ... -> via -> u.  On the lookup handle via is an entry of row(u): the
+ *             chain reads u -> via -> ... -> x.  Where several nodes qualify (a diamond) any of
+ *             them is correct, and the device and the host may pick different ones.
+ *
+ * via is a node id whatever the filter says: under a concrete type or class it may name a node
+ * that is not itself listed.  Under KETOGPU_TYPE_ANY every via is x or a listed member whose
+ * hops is one less, so the answer is a complete tree: following via from any member ends at x
+ * after hops steps.  x as a member (through a cycle, R2) has the cycle's length as hops and its
+ * predecessor on the cycle as via; a self-loop gives via == x, hops == 1.  Placeholders are
+ * never a via.  R4 snapshots, KETOGPU_NODE_NONE, never-expanded roots and ids outside the
+ * snapshot behave as in the plain calls.  No parity with ketogpu_expand is claimed: a member
+ * appears once here, and the shape does not depend on row order beyond the choice in a diamond.
+ *
+ * ketogpu_*_ids_via follows the contract of ketogpu_*_ids_depth word for word (max_depth per
+ * request, NULL or KETOGPU_DEPTH_ALL for no limit; count[i] exact; one reservation per list; a
+ * list written completely or begin[i] TRUNCATED; needed and frontier as there; capacity 0 with
+ * NULL arrays counts only).  via[k] and hops[k] belong to out[k], `capacity` words each; where a
+ * list is truncated nothing of the three arrays is written.  via and hops may each be NULL: the
+ * NULL array is not written.  ketogpu_*_page_via follows ketogpu_*_page_depth and adds via and
+ * hops of n * limit words at the same stride, valid for the first returned[i] entries of row i.
+ * The host calls return ids ascending with via and hops parallel to them (each may be NULL);
+ * their via is the parent their breadth-first search meets first.
+ *
+ * The tier rule is the depth calls'.  Tier 2 keeps a parent and a hop word per id below the
+ * member bound (num_expandable on the lookup handle, num_nodes on the subjects handle): 8 bytes
+ * x bound per slot on top of the plain calls' slots, so under the same state_budget_bytes a via
+ * round may have fewer slots; `slots` below reports them.  Via calls count only here: the plain,
+ * depth, combine and path statistics do not move.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+typedef struct {
+    uint64_t requests;       /* since creation: requests passed in                         */
+    uint64_t tier1_requests; /* answered by the one-wave LDS kernel                        */
+    uint64_t tier2_requests; /* answered by the workgroup-per-request kernel               */
+    uint64_t tier2_rounds;   /* tier-2 launches of via calls                               */
+    uint64_t list_finishes;  /* subjects handle, tier 2: finished by the seen list ...     */
+    uint64_t scan_finishes;  /* ... and by a scan of the bitmap (both 0 on the lookup handle) */
+    uint64_t cut_requests;   /* requests with a non-zero frontier                          */
+    uint64_t ids_produced;   /* sum of the exact list sizes (pages: of returned)           */
+    uint64_t truncated_lists;
+    uint32_t slots;          /* tier 2: requests per via round (0 before the first round)  */
+    double last_call_ms;     /* host wall time of the last via call                        */
+} ketogpu_via_stats;
+int ketogpu_lookup_via_stats_get(const ketogpu_lookup *l, ketogpu_via_stats *out);
+int ketogpu_subjects_via_stats_get(const ketogpu_subjects *h, ketogpu_via_stats *out);
+/* host (no GPU): *ids, *via, *hops malloc'ed, *n words each, free each with ketogpu_free; via,
+ * hops and frontier may be null */
+int ketogpu_snapshot_lookup_via(const ketogpu_snapshot *s, uint32_t target, uint32_t type, uint32_t max_depth,
+                                uint32_t **ids, uint32_t **via, uint32_t **hops, uint64_t *n, uint64_t *frontier);
+int ketogpu_snapshot_subjects_via(const ketogpu_snapshot *s, uint32_t root, uint32_t cls, uint32_t max_depth,
+                                  uint32_t **ids, uint32_t **via, uint32_t **hops, uint64_t *n, uint64_t *frontier);
+int ketogpu_lookup_ids_via(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth, size_t n,
+                           uint32_t type, uint32_t *out, uint32_t *via, uint32_t *hops, uint64_t capacity,
+                           uint64_t *begin, uint64_t *count, uint64_t *frontier, uint64_t *needed);
+int ketogpu_subjects_ids_via(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth, size_t n,
+                             uint32_t cls, uint32_t *out, uint32_t *via, uint32_t *hops, uint64_t capacity,
+                             uint64_t *begin, uint64_t *count, uint64_t *frontier, uint64_t *needed);
+int ketogpu_lookup_page_via(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth,
+                            const uint32_t *from, size_t n, uint32_t type, uint32_t limit,
+                            uint32_t *out /* n * limit words */, uint32_t *via /* n * limit words or NULL */,
+                            uint32_t *hops /* n * limit words or NULL */, uint32_t *returned, uint64_t *count,
+                            uint64_t *remaining, uint64_t *frontier);
+int ketogpu_subjects_page_via(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth,
+                              const uint32_t *from, size_t n, uint32_t cls, uint32_t limit,
+                              uint32_t *out /* n * limit words */, uint32_t *via /* n * limit words or NULL */,
+                              uint32_t *hops /* n * limit words or NULL */, uint32_t *returned, uint64_t *count,
+                              uint64_t *remaining, uint64_t *frontier);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

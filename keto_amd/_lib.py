@@ -376,6 +376,14 @@ class DepthStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# include/ketogpu.h listings that say why
+class ViaStats(C.Structure):
+    _fields_ = list(DepthStats._fields_)
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol declared in include/ketogpu.h, with its ctypes signature
 vp, i32, u32, sz = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t
 SIGNATURES = {
@@ -530,6 +538,18 @@ SIGNATURES = {
     "ketogpu_subjects_ids_depth": (C.c_int, [vp, vp, vp, sz, u32, vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]),
     "ketogpu_lookup_page_depth": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp]),
     "ketogpu_subjects_page_depth": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp]),
+    "ketogpu_lookup_via_stats_get": (C.c_int, [vp, C.POINTER(ViaStats)]),
+    "ketogpu_subjects_via_stats_get": (C.c_int, [vp, C.POINTER(ViaStats)]),
+    "ketogpu_snapshot_lookup_via": (C.c_int, [vp, u32, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ketogpu_snapshot_subjects_via": (C.c_int, [vp, u32, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_ids_via": (C.c_int, [vp, vp, vp, sz, u32, vp, vp, vp, C.c_uint64, vp, vp, vp,
+                                         C.POINTER(C.c_uint64)]),
+    "ketogpu_subjects_ids_via": (C.c_int, [vp, vp, vp, sz, u32, vp, vp, vp, C.c_uint64, vp, vp, vp,
+                                           C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_page_via": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "ketogpu_subjects_page_via": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -21,6 +21,7 @@
 #include "closure.hpp"
 #include "ketogpu_internal.hpp"
 #include "paged_finish.hpp"
+#include "via.hpp"
 
 namespace ketogpu {
 
@@ -107,8 +108,11 @@ struct ListHandle {
     DBuf<uint32_t> d_aux;              // ... and the handle's own (paths: parent words; subjects: seen lists)
     DBuf<uint32_t> d_bm2;              // combined calls: a second bitmap per slot
     DBuf<unsigned long long> d_front;  // depth calls: the frontier per request
+    DBuf<uint32_t> d_via, d_hops;      // via calls: the arrays parallel to d_out
+    DBuf<uint32_t> d_viast;            // ... and tier 2's parent and hop words: 2 x bound per slot
     uint32_t slots = 0, slot_max = 0;  // tier 2: allocated slots; what budget and knob allow (0: not yet known)
     uint32_t pair_slots = 0, pair_slot_max = 0;  // `slots` for combined calls: a slot has a second bitmap too
+    uint32_t via_slots = 0, via_slot_max = 0;    // `slots` for via calls: a slot has parent and hop words too
     uint32_t bound = 0;                // the member bound the closures take: the bitmaps span it
     uint64_t bm_words = 0;
 
@@ -119,7 +123,7 @@ struct ListHandle {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
         d_off.drop(), d_col.drop(), d_label.drop(), d_req.drop(), d_req2.drop(), d_ovf.drop(), d_out.drop();
         d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop(), d_bm.drop(), d_wl.drop();
-        d_aux.drop(), d_bm2.drop(), d_front.drop();
+        d_aux.drop(), d_bm2.drop(), d_front.drop(), d_via.drop(), d_hops.drop(), d_viast.drop();
     }
 
     double ms_of_call() const {
@@ -138,6 +142,7 @@ struct ListHandle {
         const bool moved = new_bound != bound || s.Ni != g.Ni;
         if (moved) slots = 0, slot_max = 0, d_bm.drop(), d_wl.drop(), d_aux.drop();
         if (moved) pair_slots = 0, pair_slot_max = 0, d_bm2.drop();
+        if (moved) via_slots = 0, via_slot_max = 0, d_viast.drop();
         g = closure::Rows{d_off.p, d_col.p, d_label.p, s.N, s.Nx, s.Ni};
         bound = new_bound, bm_words = ((uint64_t)bound + 31) / 32;
         version = s.version;
@@ -206,6 +211,49 @@ struct ListHandle {
         d_bm2.need(k * b2w);
         HIP_CHECK(hipMemsetAsync(d_bm2.p, 0, k * b2w * 4, stream));
         return pair_slots = (uint32_t)k;
+    }
+
+    // tier 2's state for a via call: need(k)'s slots (the handle's own need_slots, `words` words
+    // in all) plus a parent and a hop word per id below the bound in d_viast: 8 bytes x bound per
+    // slot, counted against the budget with the rest, so a via round may have fewer slots.  The
+    // words are never cleared: a bitmap bit says which of them hold.
+    template <class Need>
+    uint32_t need_via_slots(uint32_t wanted, uint64_t words, Need &&need) {
+        const uint64_t vw = 2 * std::max<uint64_t>(bound, 1);
+        uint64_t k = slots_for(wanted, words + vw, via_slot_max);
+        if (k <= via_slots && via_slots <= slots) return via_slots;
+        via_slots = 0;
+        k = std::min<uint64_t>(k, need((uint32_t)k));  // (at least one)
+        d_viast.need(k * vw);
+        return via_slots = (uint32_t)k;
+    }
+
+    // a via call's device arrays next to d_out, `words` each (null where the caller wants none)
+    via::ViaOut via_out(const uint32_t *via, const uint32_t *hops, uint64_t words) {
+        if (via) d_via.need(words);
+        if (hops) d_hops.need(words);
+        return {via ? d_via.p : nullptr, hops ? d_hops.p : nullptr};
+    }
+
+    // ... and their first `words` words back behind the call, with those of d_out where the
+    // driver has not copied them (out null: it has)
+    void read_via(uint32_t *out, uint32_t *via, uint32_t *hops, uint64_t words) {
+        if (!words || (!out && !via && !hops)) return;
+        if (out) HIP_CHECK(hipMemcpyAsync(out, d_out.p, words * 4, hipMemcpyDeviceToHost, stream));
+        if (via) HIP_CHECK(hipMemcpyAsync(via, d_via.p, words * 4, hipMemcpyDeviceToHost, stream));
+        if (hops) HIP_CHECK(hipMemcpyAsync(hops, d_hops.p, words * 4, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+
+    // where the written lists of a cursor call end.  The cursor only grows, so once a list is
+    // truncated every later reservation is: the written lists tile a prefix of `out`, and a via
+    // call copies back exactly that prefix, so that no word outside a written list is touched
+    static uint64_t written_end(const uint64_t *begin, const uint64_t *count, size_t n) {
+        uint64_t end = 0;
+        for (size_t i = 0; i < n; i++)
+            if (begin[i] != KETOGPU_LOOKUP_TRUNCATED && begin[i] != KETOGPU_LOOKUP_INVALID)
+                end = std::max<uint64_t>(end, begin[i] + count[i]);
+        return end;
     }
 
     closure::ListOut list_out(uint64_t capacity) {

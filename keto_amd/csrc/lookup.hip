@@ -25,6 +25,10 @@
 // hops of the target: the full-list and the paged kernels with depth.hpp's level bookkeeping in
 // the closures and frontier[i], the interior members the limit left unread, next to the count.
 //
+// The via calls (ketogpu_lookup_ids_via / _page_via) are the depth calls with, next to every
+// member, the node whose row granted it and its hop count: via.hpp's bodies, which keep a parent
+// and a level per first visit.
+//
 // Every index is validated before it is used: targets against num_nodes before rev_off is
 // touched, row entries against num_expandable before the type array or a bitmap is.
 #include <hip/hip_runtime.h>
@@ -33,6 +37,7 @@
 #include "depth.hpp"
 #include "hip_host.hpp"
 #include "lookup.hpp"
+#include "via.hpp"
 
 using namespace ketogpu;
 using namespace ketogpu::closure;
@@ -447,6 +452,73 @@ __global__ __launch_bounds__(kT2Block) void lookup_depth_page_tier2_kernel(
     page_report(o, i, page_count_clear(bm, bm_words, lo, ok), &s_cnt, &s_rem);
 }
 
+// ---------------------------------------------------------------------- listings that say why
+// ketogpu_lookup_ids_via / _page_via: the depth-limited listings with via[k], the node in whose
+// reverse row out[k] was first seen (an entry of row(out[k]), one hop nearer the target), and
+// hops[k], its distance (DESIGN.md "Grant trees").  The bodies are via.hpp's, over the reverse
+// rows: every id below N has a row, the member bound is Nx.  A slot adds 2 x Nx words.
+__device__ inline via::Slot lookup_via_slot(const Rows &g, uint32_t *bitmaps, uint64_t bm_words, uint32_t *worklists,
+                                            uint32_t *words) {
+    uint2 *why = reinterpret_cast<uint2 *>(words) + (uint64_t)blockIdx.x * g.Nx;
+    return {bitmaps + (uint64_t)blockIdx.x * bm_words, bm_words, worklists + (uint64_t)blockIdx.x * g.Ni, why,
+            nullptr, 0, nullptr, nullptr};
+}
+
+__global__ __launch_bounds__(64) void lookup_via_tier1_kernel(Rows g, const uint32_t *targets,
+                                                              const uint32_t *max_depth, uint32_t n, uint32_t type,
+                                                              int force_tier2, ListOut o, via::ViaOut vo,
+                                                              unsigned long long *frontier, uint32_t *ovf_list,
+                                                              unsigned int *ovf_count) {
+    __shared__ via::T1Lds s;
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    via::tier1_list(
+        g, g.Nx, g.N, targets, max_depth, i, lane, force_tier2, o, vo, frontier, ovf_list, ovf_count, s,
+        [&](uint32_t u) { return type_ok(g, u, type); }, [&](uint32_t u) { return any_type(g, u); });
+}
+
+__global__ __launch_bounds__(kT2Block) void lookup_via_tier2_kernel(Rows g, const uint32_t *targets,
+                                                                    const uint32_t *max_depth, uint32_t type,
+                                                                    ListOut o, via::ViaOut vo,
+                                                                    unsigned long long *frontier,
+                                                                    const uint32_t *ovf_list, uint32_t first,
+                                                                    uint32_t *bitmaps, uint64_t bm_words,
+                                                                    uint32_t *worklists, uint32_t *words) {
+    __shared__ via::T2Lds s;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    via::tier2_list<false>(
+        g, g.Nx, g.N, targets[i], depth::limit_of(max_depth, i), i, o, vo, frontier,
+        lookup_via_slot(g, bitmaps, bm_words, worklists, words), s, [&](uint32_t u) { return type_ok(g, u, type); },
+        [&](uint32_t u) { return any_type(g, u); });
+}
+
+__global__ __launch_bounds__(64) void lookup_via_page_tier1_kernel(Rows g, const uint32_t *targets,
+                                                                   const uint32_t *max_depth, const uint32_t *from,
+                                                                   uint32_t n, uint32_t type, int force_tier2,
+                                                                   paged::PageOut o, via::ViaOut vo,
+                                                                   unsigned long long *frontier, uint32_t *ovf_list,
+                                                                   unsigned int *ovf_count) {
+    __shared__ via::T1Lds s;
+    __shared__ uint32_t keys[kSlotsLds];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    via::tier1_page(
+        g, g.Nx, g.N, targets, max_depth, from, i, lane, force_tier2, o, vo, frontier, ovf_list, ovf_count, s, keys,
+        [&](uint32_t u) { return type_ok(g, u, type); }, [&](uint32_t u) { return any_type(g, u); });
+}
+
+__global__ __launch_bounds__(kT2Block) void lookup_via_page_tier2_kernel(
+    Rows g, const uint32_t *targets, const uint32_t *max_depth, const uint32_t *from, uint32_t type, paged::PageOut o,
+    via::ViaOut vo, unsigned long long *frontier, const uint32_t *ovf_list, uint32_t first, uint32_t *bitmaps,
+    uint64_t bm_words, uint32_t *worklists, uint32_t *words) {
+    __shared__ via::T2Lds s;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    via::tier2_page<false>(
+        g, g.Nx, g.N, targets[i], depth::limit_of(max_depth, i), from[i], i, o, vo, frontier,
+        lookup_via_slot(g, bitmaps, bm_words, worklists, words), s, [&](uint32_t u) { return type_ok(g, u, type); },
+        [&](uint32_t u) { return any_type(g, u); });
+}
+
 }  // namespace
 
 struct ketogpu_lookup : ListHandle {
@@ -455,6 +527,7 @@ struct ketogpu_lookup : ListHandle {
     ketogpu_lookup_path_stats pst{};
     ketogpu_combine_stats cst{};
     ketogpu_depth_stats dst{};
+    ketogpu_via_stats vst{};
 
     ketogpu_lookup() : ListHandle("reverse lookup") {}
 
@@ -629,6 +702,59 @@ struct ketogpu_lookup : ListHandle {
         dst.cut_requests += read_frontier(frontier, n);
         dst.last_call_ms = ms_of_call();
     }
+
+    // tier 2's state for a via call (ListHandle::need_via_slots)
+    uint32_t need_via_state(uint32_t wanted) {
+        return vst.slots = need_via_slots(wanted, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+    }
+
+    // ketogpu_lookup_ids_via: run_depth() with via and hops next to out
+    void run_via(const uint32_t *targets, const uint32_t *max_depth, size_t n, uint32_t type, uint32_t *out,
+                 uint32_t *via, uint32_t *hops, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                 uint64_t *frontier, uint64_t *needed) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        const via::ViaOut vo = via_out(via, hops, capacity);
+        run_cursor(
+            vst, targets, n, nullptr, capacity, begin, count, needed,  // (the ids come back with via and hops)
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || targets[i] == NONE; },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_via_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        (uint32_t)n, type, force_tier2 ? 1 : 0, list_out(capacity), vo, d_front.p, d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return need_via_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(lookup_via_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_depth, type,
+                        list_out(capacity), vo, d_front.p, d_ovf.p, first, d_bm.p, bm_words, d_wl.p, d_viast.p);
+            });
+        read_via(out, via, hops, written_end(begin, count, n));
+        vst.cut_requests += read_frontier(frontier, n);
+        vst.last_call_ms = ms_of_call();
+    }
+
+    // ketogpu_lookup_page_via: run_page_depth() with via and hops at the stride of out
+    void run_page_via(const uint32_t *targets, const uint32_t *max_depth, const uint32_t *from, size_t n,
+                      uint32_t type, uint32_t limit, uint32_t *out, uint32_t *via, uint32_t *hops, uint32_t *returned,
+                      uint64_t *count, uint64_t *remaining, uint64_t *frontier) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        const via::ViaOut vo = via_out(via, hops, n * (uint64_t)limit);
+        ListHandle::run_page(
+            vst, targets, from, n, limit, out, returned, count, remaining,
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_via_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        d_from.p, (uint32_t)n, type, force_tier2 ? 1 : 0, page_out(limit), vo, d_front.p, d_ovf.p,
+                        ovf_count);
+            },
+            [&](uint32_t ovf) { return need_via_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(lookup_via_page_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_depth,
+                        d_from.p, type, page_out(limit), vo, d_front.p, d_ovf.p, first, d_bm.p, bm_words, d_wl.p,
+                        d_viast.p);
+            },
+            [](Tally &) {});
+        read_via(nullptr, via, hops, n * (uint64_t)limit);
+        vst.cut_requests += read_frontier(frontier, n);
+        vst.last_call_ms = ms_of_call();
+    }
 };
 
 extern "C" {
@@ -703,6 +829,30 @@ int ketogpu_lookup_page_depth(ketogpu_lookup *l, const uint32_t *targets, const 
                               uint32_t *returned, uint64_t *count, uint64_t *remaining, uint64_t *frontier) {
     return list_call(l, n && (!targets || !out || !returned || !count || !remaining), n, "targets", &limit, [&] {
         l->run_page_depth(targets, max_depth, from, n, type, limit, out, returned, count, remaining, frontier);
+    });
+}
+
+int ketogpu_lookup_via_stats_get(const ketogpu_lookup *l, ketogpu_via_stats *out) {
+    return list_stats_get(l, &ketogpu_lookup::vst, out);
+}
+
+int ketogpu_lookup_ids_via(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth, size_t n,
+                           uint32_t type, uint32_t *out, uint32_t *via, uint32_t *hops, uint64_t capacity,
+                           uint64_t *begin, uint64_t *count, uint64_t *frontier, uint64_t *needed) {
+    return list_call(l, !needed || (n && (!targets || !begin || !count)) || (capacity && !out), n, "targets", nullptr,
+                     [&] {
+                         l->run_via(targets, max_depth, n, type, out, capacity ? via : nullptr,
+                                    capacity ? hops : nullptr, capacity, begin, count, frontier, needed);
+                     });
+}
+
+int ketogpu_lookup_page_via(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth,
+                            const uint32_t *from, size_t n, uint32_t type, uint32_t limit, uint32_t *out,
+                            uint32_t *via, uint32_t *hops, uint32_t *returned, uint64_t *count, uint64_t *remaining,
+                            uint64_t *frontier) {
+    return list_call(l, n && (!targets || !out || !returned || !count || !remaining), n, "targets", &limit, [&] {
+        l->run_page_via(targets, max_depth, from, n, type, limit, out, via, hops, returned, count, remaining,
+                        frontier);
     });
 }
 

@@ -29,4 +29,14 @@ inline bool type_matches(uint32_t node_type, uint32_t want) {
     return want == KETOGPU_TYPE_ANY ? node_type != KETOGPU_TYPE_NONE : (want != KETOGPU_TYPE_NONE && node_type == want);
 }
 
+// one member of a host via call (ketogpu_snapshot_*_via): its id, the node whose row it was
+// first seen in, and its distance from the start
+struct ViaEntry {
+    uint32_t id, via, hops;
+};
+
+// the members, ascending by id, to three malloc'ed arrays of *n words (via and hops may be
+// null: not wanted); nothing is left allocated when this throws.  In lookup_host.cpp.
+void via_result(std::vector<ViaEntry> &res, uint32_t **ids, uint32_t **via, uint32_t **hops, uint64_t *n);
+
 }  // namespace ketogpu

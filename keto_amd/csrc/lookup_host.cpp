@@ -35,6 +35,27 @@ std::shared_ptr<const TypeIndex> type_index_of(const Snapshot &s) {
     return t;
 }
 
+void via_result(std::vector<ViaEntry> &res, uint32_t **ids, uint32_t **via, uint32_t **hops, uint64_t *n) {
+    std::sort(res.begin(), res.end(), [](const ViaEntry &a, const ViaEntry &b) { return a.id < b.id; });
+    const size_t bytes = std::max<size_t>(res.size(), 1) * sizeof(uint32_t);
+    uint32_t *p = (uint32_t *)malloc(bytes);
+    uint32_t *pv = via ? (uint32_t *)malloc(bytes) : nullptr;
+    uint32_t *ph = hops ? (uint32_t *)malloc(bytes) : nullptr;
+    if (!p || (via && !pv) || (hops && !ph)) {
+        free(p), free(pv), free(ph);
+        throw std::bad_alloc();
+    }
+    for (size_t k = 0; k < res.size(); k++) {
+        p[k] = res[k].id;
+        if (pv) pv[k] = res[k].via;
+        if (ph) ph[k] = res[k].hops;
+    }
+    *ids = p;
+    if (via) *via = pv;
+    if (hops) *hops = ph;
+    *n = res.size();
+}
+
 }  // namespace ketogpu
 
 using namespace ketogpu;
@@ -186,6 +207,68 @@ int ketogpu_snapshot_lookup_depth(const ketogpu_snapshot *sp, uint32_t target, u
         if (!res.empty()) memcpy(p, res.data(), res.size() * sizeof(uint32_t));
         *ids = p;
         *n = res.size();
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
+
+// ketogpu_snapshot_lookup_depth with the parent and the level of every first visit kept
+// (DESIGN.md "Grant trees"): via is the node whose reverse row the member was first seen in,
+// hops the level of that row plus one.
+int ketogpu_snapshot_lookup_via(const ketogpu_snapshot *sp, uint32_t target, uint32_t type, uint32_t max_depth,
+                                uint32_t **ids, uint32_t **via, uint32_t **hops, uint64_t *n, uint64_t *frontier) {
+    if (!sp || !ids || !n) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *ids = nullptr;
+    if (via) *via = nullptr;
+    if (hops) *hops = nullptr;
+    *n = 0;
+    if (frontier) *frontier = 0;
+    try {
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        std::shared_lock<std::shared_mutex> rd(s.mu);
+        if (s.has_ambiguous)
+            throw Error(KETOGPU_EINVAL, "reverse lookup: the snapshot has shared Subject.String() keys (R4)");
+        if (target != NONE && target >= s.N) throw Error(KETOGPU_EINVAL, "target outside the snapshot");
+        std::vector<ViaEntry> res;
+        if (target != NONE) {
+            auto types = type_index_of(s);
+            std::unordered_set<uint32_t> seen;
+            std::vector<uint32_t> work;
+            uint32_t level = 0;  // of the row at hand (the target's: 0)
+            auto row = [&](uint32_t v) {
+                for (uint64_t j = s.rev_off[v]; j < s.rev_off[v + 1]; j++) {
+                    const uint32_t u = s.rev_col[j];
+                    if (!seen.insert(u).second) continue;
+                    if (u < s.Ni) work.push_back(u);
+                    if (u < s.Nx && type_matches(types->node_type[u], type)) res.push_back({u, v, level + 1});
+                }
+            };
+            row(target);
+            size_t head = 0, level_end = 0;  // the row at hand is of `level`, which ends at work[level_end)
+            for (;;) {
+                if (head == level_end) {  // work[head ..) is the next level
+                    level++;
+                    level_end = work.size();
+                    if (head == work.size()) break;
+                    if (level == max_depth) {  // (a placeholder is interior, but no member)
+                        uint64_t fr = 0;
+                        for (size_t k = head; k < work.size(); k++) fr += types->node_type[work[k]] != KETOGPU_TYPE_NONE;
+                        if (frontier) *frontier = fr;
+                        break;
+                    }
+                }
+                row(work[head++]);
+            }
+        }
+        via_result(res, ids, via, hops, n);
         return KETOGPU_OK;
     } catch (const Error &e) {
         set_last_error(e.what());

@@ -29,6 +29,10 @@
 // bookkeeping in the closures, both tier-2 finishes, and frontier[i], the interior members the
 // limit left unread, next to the count.
 //
+// The via calls (ketogpu_subjects_ids_via / _page_via) are the depth calls with, next to every
+// member, the node whose row granted it and its hop count: via.hpp's bodies, which keep a parent
+// and a level per first visit.
+//
 // Every index is validated before it is used: roots against N, and against Nx before fwd_off
 // is touched; row entries against N before the class array or a bitmap is.
 #include <hip/hip_runtime.h>
@@ -37,6 +41,7 @@
 #include "depth.hpp"
 #include "hip_host.hpp"
 #include "subjects.hpp"
+#include "via.hpp"
 
 using namespace ketogpu;
 using namespace ketogpu::closure;
@@ -444,6 +449,78 @@ __global__ __launch_bounds__(kT2Block) void subjects_depth_page_tier2_kernel(
     if (tid == 0) atomicAdd(by_list ? list_finishes : scan_finishes, 1ull);
 }
 
+// ---------------------------------------------------------------------- listings that say why
+// ketogpu_subjects_ids_via / _page_via: the depth-limited listings with via[k], the node in
+// whose row out[k] was first seen (out[k] is an entry of row(via[k]), one hop nearer the root),
+// and hops[k], its distance (DESIGN.md "Grant trees").  The bodies are via.hpp's, over the
+// forward rows: the ids below Nx have a row, the member bound is N; both tier-2 finishes are
+// kept.  A slot adds 2 x N words.
+__device__ inline via::Slot subjects_via_slot(const Rows &g, uint32_t *bitmaps, uint64_t bm_words,
+                                              uint32_t *worklists, uint32_t *seen_lists, uint32_t list_cap,
+                                              uint32_t *words, unsigned long long *list_finishes,
+                                              unsigned long long *scan_finishes) {
+    uint2 *why = reinterpret_cast<uint2 *>(words) + (uint64_t)blockIdx.x * g.N;
+    return {bitmaps + (uint64_t)blockIdx.x * bm_words, bm_words, worklists + (uint64_t)blockIdx.x * g.Ni, why,
+            seen_lists + (uint64_t)blockIdx.x * list_cap, list_cap, list_finishes, scan_finishes};
+}
+
+__global__ __launch_bounds__(64) void subjects_via_tier1_kernel(Rows g, const uint32_t *roots,
+                                                                const uint32_t *max_depth, uint32_t n, uint32_t cls,
+                                                                int force_tier2, ListOut o, via::ViaOut vo,
+                                                                unsigned long long *frontier, uint32_t *ovf_list,
+                                                                unsigned int *ovf_count) {
+    __shared__ via::T1Lds s;
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    via::tier1_list(
+        g, g.N, g.Nx, roots, max_depth, i, lane, force_tier2, o, vo, frontier, ovf_list, ovf_count, s,
+        [&](uint32_t u) { return class_ok(g, u, cls); }, [&](uint32_t u) { return any_class(g, u); });
+}
+
+__global__ __launch_bounds__(kT2Block) void subjects_via_tier2_kernel(Rows g, const uint32_t *roots,
+                                                                      const uint32_t *max_depth, uint32_t cls, SOut o,
+                                                                      via::ViaOut vo, unsigned long long *frontier,
+                                                                      const uint32_t *ovf_list, uint32_t first,
+                                                                      uint32_t *bitmaps, uint64_t bm_words,
+                                                                      uint32_t *worklists, uint32_t *seen_lists,
+                                                                      uint32_t list_cap, uint32_t *words) {
+    __shared__ via::T2Lds s;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    via::tier2_list<true>(
+        g, g.N, g.Nx, roots[i], depth::limit_of(max_depth, i), i, o.l, vo, frontier,
+        subjects_via_slot(g, bitmaps, bm_words, worklists, seen_lists, list_cap, words, o.list_finishes,
+                          o.scan_finishes),
+        s, [&](uint32_t u) { return class_ok(g, u, cls); }, [&](uint32_t u) { return any_class(g, u); });
+}
+
+__global__ __launch_bounds__(64) void subjects_via_page_tier1_kernel(Rows g, const uint32_t *roots,
+                                                                     const uint32_t *max_depth, const uint32_t *from,
+                                                                     uint32_t n, uint32_t cls, int force_tier2,
+                                                                     paged::PageOut o, via::ViaOut vo,
+                                                                     unsigned long long *frontier, uint32_t *ovf_list,
+                                                                     unsigned int *ovf_count) {
+    __shared__ via::T1Lds s;
+    __shared__ uint32_t keys[kSlotsLds];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    via::tier1_page(
+        g, g.N, g.Nx, roots, max_depth, from, i, lane, force_tier2, o, vo, frontier, ovf_list, ovf_count, s, keys,
+        [&](uint32_t u) { return class_ok(g, u, cls); }, [&](uint32_t u) { return any_class(g, u); });
+}
+
+__global__ __launch_bounds__(kT2Block) void subjects_via_page_tier2_kernel(
+    Rows g, const uint32_t *roots, const uint32_t *max_depth, const uint32_t *from, uint32_t cls, paged::PageOut o,
+    via::ViaOut vo, unsigned long long *frontier, unsigned long long *list_finishes,
+    unsigned long long *scan_finishes, const uint32_t *ovf_list, uint32_t first, uint32_t *bitmaps, uint64_t bm_words,
+    uint32_t *worklists, uint32_t *seen_lists, uint32_t list_cap, uint32_t *words) {
+    __shared__ via::T2Lds s;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    via::tier2_page<true>(
+        g, g.N, g.Nx, roots[i], depth::limit_of(max_depth, i), from[i], i, o, vo, frontier,
+        subjects_via_slot(g, bitmaps, bm_words, worklists, seen_lists, list_cap, words, list_finishes, scan_finishes),
+        s, [&](uint32_t u) { return class_ok(g, u, cls); }, [&](uint32_t u) { return any_class(g, u); });
+}
+
 }  // namespace
 
 struct ketogpu_subjects : ListHandle {
@@ -453,6 +530,7 @@ struct ketogpu_subjects : ListHandle {
     ketogpu_subjects_stats st{};
     ketogpu_combine_stats cst{};
     ketogpu_depth_stats dst{};
+    ketogpu_via_stats vst{};
 
     ketogpu_subjects() : ListHandle("subject listing") {}
 
@@ -611,6 +689,66 @@ struct ketogpu_subjects : ListHandle {
             frontier, n);
     }
 
+    // tier 2's state for a via call (ListHandle::need_via_slots): the handle's slots as they are,
+    // seen lists included
+    uint32_t need_via_state(uint32_t wanted) {
+        return vst.slots = need_via_slots(wanted, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+    }
+
+    // ketogpu_subjects_ids_via: run_depth() with via and hops next to out
+    void run_via(const uint32_t *roots, const uint32_t *max_depth, size_t n, uint32_t cls, uint32_t *out,
+                 uint32_t *via, uint32_t *hops, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                 uint64_t *frontier, uint64_t *needed) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        const via::ViaOut vo = via_out(via, hops, capacity);
+        const Tally t = run_cursor(
+            vst, roots, n, nullptr, capacity, begin, count, needed,  // (the ids come back with via and hops)
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || roots[i] == NONE; },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_via_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        (uint32_t)n, cls, force_tier2 ? 1 : 0, list_out(capacity), vo, d_front.p, d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return need_via_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(subjects_via_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_depth, cls,
+                        subjects_out(capacity), vo, d_front.p, d_ovf.p, first, d_bm.p, bm_words, d_wl.p, d_aux.p,
+                        list_cap, d_viast.p);
+            });
+        read_via(out, via, hops, written_end(begin, count, n));
+        count_via_finishes(t, frontier, n);
+    }
+
+    // ketogpu_subjects_page_via: run_page_depth() with via and hops at the stride of out
+    void run_page_via(const uint32_t *roots, const uint32_t *max_depth, const uint32_t *from, size_t n, uint32_t cls,
+                      uint32_t limit, uint32_t *out, uint32_t *via, uint32_t *hops, uint32_t *returned,
+                      uint64_t *count, uint64_t *remaining, uint64_t *frontier) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        const via::ViaOut vo = via_out(via, hops, n * (uint64_t)limit);
+        const Tally t = ListHandle::run_page(
+            vst, roots, from, n, limit, out, returned, count, remaining,
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_via_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        d_from.p, (uint32_t)n, cls, force_tier2 ? 1 : 0, page_out(limit), vo, d_front.p, d_ovf.p,
+                        ovf_count);
+            },
+            [&](uint32_t ovf) { return need_via_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(subjects_via_page_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, d_depth,
+                        d_from.p, cls, page_out(limit), vo, d_front.p, d_ctr.p + 3, d_ctr.p + 4, d_ovf.p, first,
+                        d_bm.p, bm_words, d_wl.p, d_aux.p, list_cap, d_viast.p);
+            },
+            [&](Tally &t) { read_ctrs(t); });  // (the finish counters)
+        read_via(nullptr, via, hops, n * (uint64_t)limit);
+        count_via_finishes(t, frontier, n);
+    }
+
+    void count_via_finishes(const Tally &t, uint64_t *frontier, size_t n) {
+        vst.list_finishes += t.ctr[3];
+        vst.scan_finishes += t.ctr[4];
+        vst.cut_requests += read_frontier(frontier, n);
+        vst.last_call_ms = ms_of_call();
+    }
+
     void count_depth_finishes(const Tally &t, uint64_t *frontier, size_t n) {
         dst.list_finishes += t.ctr[3];
         dst.scan_finishes += t.ctr[4];
@@ -691,6 +829,29 @@ int ketogpu_subjects_page_depth(ketogpu_subjects *h, const uint32_t *roots, cons
                                 uint32_t *returned, uint64_t *count, uint64_t *remaining, uint64_t *frontier) {
     return list_call(h, n && (!roots || !out || !returned || !count || !remaining), n, "roots", &limit, [&] {
         h->run_page_depth(roots, max_depth, from, n, cls, limit, out, returned, count, remaining, frontier);
+    });
+}
+
+int ketogpu_subjects_via_stats_get(const ketogpu_subjects *h, ketogpu_via_stats *out) {
+    return list_stats_get(h, &ketogpu_subjects::vst, out);
+}
+
+int ketogpu_subjects_ids_via(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth, size_t n,
+                             uint32_t cls, uint32_t *out, uint32_t *via, uint32_t *hops, uint64_t capacity,
+                             uint64_t *begin, uint64_t *count, uint64_t *frontier, uint64_t *needed) {
+    return list_call(h, !needed || (n && (!roots || !begin || !count)) || (capacity && !out), n, "roots", nullptr,
+                     [&] {
+                         h->run_via(roots, max_depth, n, cls, out, capacity ? via : nullptr,
+                                    capacity ? hops : nullptr, capacity, begin, count, frontier, needed);
+                     });
+}
+
+int ketogpu_subjects_page_via(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth,
+                              const uint32_t *from, size_t n, uint32_t cls, uint32_t limit, uint32_t *out,
+                              uint32_t *via, uint32_t *hops, uint32_t *returned, uint64_t *count, uint64_t *remaining,
+                              uint64_t *frontier) {
+    return list_call(h, n && (!roots || !out || !returned || !count || !remaining), n, "roots", &limit, [&] {
+        h->run_page_via(roots, max_depth, from, n, cls, limit, out, via, hops, returned, count, remaining, frontier);
     });
 }
 

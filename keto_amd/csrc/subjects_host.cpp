@@ -170,4 +170,68 @@ int ketogpu_snapshot_subjects_depth(const ketogpu_snapshot *sp, uint32_t root, u
     }
 }
 
+// ketogpu_snapshot_subjects_depth with the parent and the level of every first visit kept
+// (DESIGN.md "Grant trees"): via is the node whose row the member was first seen in, hops the
+// level of that row plus one.
+int ketogpu_snapshot_subjects_via(const ketogpu_snapshot *sp, uint32_t root, uint32_t cls, uint32_t max_depth,
+                                  uint32_t **ids, uint32_t **via, uint32_t **hops, uint64_t *n, uint64_t *frontier) {
+    if (!sp || !ids || !n) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *ids = nullptr;
+    if (via) *via = nullptr;
+    if (hops) *hops = nullptr;
+    *n = 0;
+    if (frontier) *frontier = 0;
+    try {
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        std::shared_lock<std::shared_mutex> rd(s.mu);
+        if (s.has_ambiguous)
+            throw Error(KETOGPU_EINVAL, "subject listing: the snapshot has shared Subject.String() keys (R4)");
+        if (root != NONE && root >= s.N) throw Error(KETOGPU_EINVAL, "root outside the snapshot");
+        std::vector<ViaEntry> res;
+        if (root < s.Nx) {  // (NONE and the never-expanded nodes: the empty list)
+            auto classes = class_index_of(s);
+            std::unordered_set<uint32_t> seen;
+            std::vector<uint32_t> work;
+            uint32_t level = 0;  // of the row at hand (the root's: 0)
+            auto row = [&](uint32_t v) {
+                const uint32_t *p = s.row_ptr(v);
+                for (uint32_t j = 0; j < s.node_row[v].len; j++) {
+                    const uint32_t u = p[j];
+                    if (u >= s.N || !seen.insert(u).second) continue;
+                    if (u < s.Ni) work.push_back(u);
+                    if (class_matches(classes->node_class[u], cls)) res.push_back({u, v, level + 1});
+                }
+            };
+            row(root);
+            size_t head = 0, level_end = 0;  // the row at hand is of `level`, which ends at work[level_end)
+            for (;;) {
+                if (head == level_end) {  // work[head ..) is the next level
+                    level++;
+                    level_end = work.size();
+                    if (head == work.size()) break;
+                    if (level == max_depth) {  // (a placeholder is interior, but no member)
+                        uint64_t fr = 0;
+                        for (size_t k = head; k < work.size(); k++)
+                            fr += classes->node_class[work[k]] != KETOGPU_TYPE_NONE;
+                        if (frontier) *frontier = fr;
+                        break;
+                    }
+                }
+                row(work[head++]);
+            }
+        }
+        via_result(res, ids, via, hops, n);
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
+
 }  // extern "C"

@@ -12,6 +12,8 @@ caller gets the reference's responses from the new engines:
     GET  /list/subjects  (new, same section)                     200 {"subjects": [...], "next_page_token", "total"}
          both take max-depth (Keto's spelling; DESIGN.md "Depth-limited listings"): a positive integer, else 400;
          the list within that many hops, and the body gains "complete": true | false
+         both take via=true (DESIGN.md "Grant trees"; any other value is 400): every entry becomes
+         {"object" | "subject": ..., "via": the granting subject, "hops": n}
     GET  /list/objects/combined, /list/subjects/combined  (new, DESIGN.md "Combined listings")  the same bodies for
          the list of two subjects / two objects under op = and | andnot | or
     GET  /check/explain  (new, DESIGN.md "Explain")  200 {"allowed":true,"path":[...]} | 403 {"allowed":false,"path":[]}
@@ -278,6 +280,17 @@ class Handler:
             raise BadRequest(f"max-depth {depth} is not a positive integer")
         return min(depth, 0xFFFFFFFF)  # (every depth beyond any closure's acts the same)
 
+    @staticmethod
+    def _via(q):
+        """via -> False when the parameter is absent, True for "true"; anything else is a
+        BadRequest"""
+        if "via" not in q:
+            return False
+        raw = _get(q, "via")
+        if raw != "true":
+            raise BadRequest(f'via {json.dumps(raw or "")}: expected "true"')
+        return True
+
     def _list(self, backend, query, call):
         if backend is None:
             return self._error(404, "this server has no list handle")
@@ -295,10 +308,19 @@ class Handler:
     def get_list_objects(self, query):
         """namespace, relation, subject_id | subject_set.*, page_size, page_token -> the objects o
         with Check(namespace:o#relation@subject); with max-depth, those within that many hops
-        of the subject, and "complete" """
+        of the subject, and "complete"; with via=true every entry is {"object", "via", "hops"} """
         def call(q, size, token):
             depth = self._max_depth(q)
+            why = self._via(q)
             t = tuple_from_url(q)  # the subject is required
+            if why:
+                res = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size, token, max_depth=depth,
+                                                    with_via=True)
+                body = {"objects": [{"object": o, "via": v.to_dict(), "hops": h} for o, v, h in res[0]],
+                        "next_page_token": res[1], "total": res[2]}
+                if depth is not None:
+                    body["complete"] = bool(res[3])
+                return body
             if depth is not None:
                 items, nxt, total, complete = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size,
                                                                             token, max_depth=depth)
@@ -310,9 +332,11 @@ class Handler:
     def get_list_subjects(self, query):
         """namespace, object, relation, kind (ids | any | ns#relation), page_size, page_token -> the
         subjects s with Check(namespace:object#relation@s), in the JSON form check requests use;
-        with max-depth, those within that many hops of the object, and "complete" """
+        with max-depth, those within that many hops of the object, and "complete"; with via=true
+        every entry is {"subject", "via", "hops"} """
         def call(q, size, token):
             depth = self._max_depth(q)
+            why = self._via(q)
             kind = _get(q, "kind") or "ids"
             if kind not in ("ids", "any"):
                 ns, sep, rel = kind.partition("#")
@@ -320,6 +344,13 @@ class Handler:
                     raise BadRequest(f'kind {kind!r}: expected "ids", "any" or "namespace#relation"')
                 kind = (ns, rel)
             root = (_get(q, "namespace") or "", _get(q, "object") or "", _get(q, "relation") or "")
+            if why:
+                res = self.subjects.list_subjects_page(*root, kind, size, token, max_depth=depth, with_via=True)
+                body = {"subjects": [{"subject": s.to_dict(), "via": v.to_dict(), "hops": h} for s, v, h in res[0]],
+                        "next_page_token": res[1], "total": res[2]}
+                if depth is not None:
+                    body["complete"] = bool(res[3])
+                return body
             if depth is not None:
                 items, nxt, total, complete = self.subjects.list_subjects_page(*root, kind, size, token,
                                                                                max_depth=depth)

@@ -119,10 +119,13 @@ def _page_args(ids, from_ids, limit):
 class _ObjectPages:
     """list_objects_page over self.lookup_page_raw and self.snapshot"""
 
-    def list_objects_page_batch(self, namespace, relation, requests, page_size=100, max_depth=None):
+    def list_objects_page_batch(self, namespace, relation, requests, page_size=100, max_depth=None, with_via=False):
         """requests: (subject, page_token) pairs, one device call for all of them -> per
         request (object names in node-id order, next_page_token, total).  max_depth (one number,
-        or one per request): the objects within that many hops, and a fourth element `complete`"""
+        or one per request): the objects within that many hops, and a fourth element `complete`.
+        with_via: every item is (name, via, hops), via the subject the granting node stands for"""
+        if with_via:
+            return self._list_objects_page_via(namespace, relation, list(requests), page_size, max_depth)
         if max_depth is not None:
             return self._list_objects_page_depth(namespace, relation, list(requests), page_size, max_depth)
         page_size = check_page_size(page_size)
@@ -140,11 +143,33 @@ class _ObjectPages:
             res.append((names, next_page_token(out[i], k, remaining[i]), int(count[i])))
         return res
 
-    def list_objects_page(self, namespace, relation, subject, page_size=100, page_token="", max_depth=None):
+    def list_objects_page(self, namespace, relation, subject, page_size=100, page_token="", max_depth=None,
+                          with_via=False):
         """-> (items, next_page_token, total): at most page_size object names o with
         Check(namespace:o#relation@subject), in node-id order from the token on.  With max_depth:
-        of the objects within that many hops, -> (items, next_page_token, total, complete)"""
-        return self.list_objects_page_batch(namespace, relation, [(subject, page_token)], page_size, max_depth)[0]
+        of the objects within that many hops, -> (items, next_page_token, total, complete).  With
+        with_via the items are (name, via, hops)"""
+        return self.list_objects_page_batch(namespace, relation, [(subject, page_token)], page_size, max_depth,
+                                            with_via)[0]
+
+    def _list_objects_page_via(self, namespace, relation, requests, page_size, max_depth):
+        page_size = check_page_size(page_size)
+        lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
+        depth = depth_array(max_depth, len(requests))
+        ty = self.snapshot.type_id(namespace, relation)
+        targets = resolve_subjects(self.snapshot, [s for s, _ in requests])
+        tail = lambda complete: () if max_depth is None else (complete,)
+        if ty == TYPE_NONE:
+            return [([], "", 0) + tail(True) for _ in requests]
+        out, via, hops, returned, count, remaining, frontier = self.lookup_via_page_raw(targets, depth, lo, ty,
+                                                                                        page_size)
+        res = []
+        for i in range(len(requests)):
+            k = int(returned[i])
+            items = [(self.snapshot.node_info(int(v))["id"], self.snapshot.describe(int(w)), int(h))
+                     for v, w, h in zip(out[i, :k], via[i, :k], hops[i, :k])]
+            res.append((items, next_page_token(out[i], k, remaining[i]), int(count[i])) + tail(not frontier[i]))
+        return res
 
     def _list_objects_page_depth(self, namespace, relation, requests, page_size, max_depth):
         page_size = check_page_size(page_size)
@@ -166,11 +191,14 @@ class _ObjectPages:
 class _SubjectPages:
     """list_subjects_page over self.subject_page_raw and self.snapshot"""
 
-    def list_subjects_page_batch(self, requests, kind="ids", page_size=100, max_depth=None):
+    def list_subjects_page_batch(self, requests, kind="ids", page_size=100, max_depth=None, with_via=False):
         """requests: ((namespace, object, relation), page_token) pairs, one device call for all
         of them -> per request (SubjectID / SubjectSet in node-id order, next_page_token, total).
         max_depth (one number, or one per request): the subjects within that many hops, and a
-        fourth element `complete`"""
+        fourth element `complete`.  with_via: every item is (subject, via, hops), via the subject
+        set whose tuple grants it"""
+        if with_via:
+            return self._list_subjects_page_via(list(requests), kind, page_size, max_depth)
         if max_depth is not None:
             return self._list_subjects_page_depth(list(requests), kind, page_size, max_depth)
         page_size = check_page_size(page_size)
@@ -189,12 +217,32 @@ class _SubjectPages:
         return res
 
     def list_subjects_page(self, namespace, object, relation, kind="ids", page_size=100, page_token="",
-                           max_depth=None):
+                           max_depth=None, with_via=False):
         """-> (items, next_page_token, total): at most page_size subjects s with
         Check(namespace:object#relation@s), in node-id order from the token on.  With max_depth:
-        of the subjects within that many hops, -> (items, next_page_token, total, complete)"""
+        of the subjects within that many hops, -> (items, next_page_token, total, complete).  With
+        with_via the items are (subject, via, hops)"""
         return self.list_subjects_page_batch([((namespace, object, relation), page_token)], kind, page_size,
-                                             max_depth)[0]
+                                             max_depth, with_via)[0]
+
+    def _list_subjects_page_via(self, requests, kind, page_size, max_depth):
+        page_size = check_page_size(page_size)
+        lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
+        depth = depth_array(max_depth, len(requests))
+        cls = _class_of_kind(self.snapshot, kind)
+        roots = resolve_roots(self.snapshot, [tuple(r) for r, _ in requests])
+        tail = lambda complete: () if max_depth is None else (complete,)
+        if cls == TYPE_NONE:
+            return [([], "", 0) + tail(True) for _ in requests]
+        out, via, hops, returned, count, remaining, frontier = self.subject_via_page_raw(roots, depth, lo, cls,
+                                                                                         page_size)
+        res = []
+        for i in range(len(requests)):
+            k = int(returned[i])
+            items = [(self.snapshot.describe(int(v)), self.snapshot.describe(int(w)), int(h))
+                     for v, w, h in zip(out[i, :k], via[i, :k], hops[i, :k])]
+            res.append((items, next_page_token(out[i], k, remaining[i]), int(count[i])) + tail(not frontier[i]))
+        return res
 
     def _list_subjects_page_depth(self, requests, kind, page_size, max_depth):
         page_size = check_page_size(page_size)
@@ -341,6 +389,167 @@ class _SubjectsDepth:
             return [[] for _ in roots], [True] * len(roots)
         lists, frontier = self.subject_depth(ids, depth, cls)
         return [_subjects_of(self.snapshot, v) for v in lists], [not f for f in frontier]
+
+
+# ---- listings that say why (include/ketogpu.h "listings that say why", DESIGN.md "Grant
+# trees"), shared by the device handles and their CPU twins
+def grant_chain(ids, via, start, u):
+    """one member's chain to the start over an answer under TYPE_ANY (ids ascending, via parallel
+    to them) -> [u, via(u), via(via(u)), ..., start]: hops(u) + 1 nodes.  Only an ANY answer is a
+    complete tree; a via that is neither the start nor a listed member raises KeyError"""
+    ids = np.asarray(ids)
+    chain, cur = [int(u)], int(u)
+    for _ in range(len(ids) + 1):
+        k = int(np.searchsorted(ids, cur))
+        if k >= len(ids) or int(ids[k]) != cur:
+            raise KeyError(f"node {cur} is not a member of this answer")
+        cur = int(via[k])
+        chain.append(cur)
+        if cur == int(start):
+            return chain
+    raise KeyError(f"the chain of {int(u)} does not end at {int(start)}")
+
+
+def _via_lists(raw, ids, max_depth, cap):
+    """every list of a via call raw(ids, depth, cap) -> (out, via, hops, begin, count, frontier,
+    needed), with _all_lists' re-issue of truncated lists -> (per request (ids ascending, via,
+    hops), frontier)"""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    depth = depth_array(max_depth, len(ids))
+    n = len(ids)
+    frontier = np.zeros(n, dtype=np.uint64)
+    res = [None] * n
+    idx = np.arange(n)
+    cap = 64 * n if cap is None else int(cap)
+    while len(idx):
+        out, via, hops, begin, count, fr, _ = raw(ids[idx], None if depth is None else depth[idx], cap)
+        frontier[idx] = fr
+        if (begin == INVALID).any():
+            raise L.KetoError(L.EINVAL, f"id {int(ids[idx[begin == INVALID][0]])} is outside the snapshot")
+        done = begin != TRUNCATED
+        for k in np.nonzero(done)[0]:
+            b, c = int(begin[k]), int(count[k])
+            order = np.argsort(out[b:b + c], kind="stable")
+            res[idx[k]] = (out[b:b + c][order], via[b:b + c][order], hops[b:b + c][order])
+        cap = int(count[~done].sum())  # exactly what the rest needs: nothing is truncated twice
+        idx = idx[~done]
+    return res, frontier
+
+
+def _host_via(snapshot, call, x, filter_id, max_depth):
+    """one ketogpu_snapshot_*_via call -> (ids ascending, via, hops (uint32 each), frontier)"""
+    p, pv, ph, n, fr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+    lib = snapshot.L
+    L.check(getattr(lib, call)(snapshot.h, int(x), int(filter_id), int(max_depth), C.byref(p), C.byref(pv),
+                               C.byref(ph), C.byref(n), C.byref(fr)))
+    try:
+        return tuple(np.ctypeslib.as_array(C.cast(q, C.POINTER(C.c_uint32)), (n.value,)).copy() if n.value
+                     else np.zeros(0, dtype=np.uint32) for q in (p, pv, ph)) + (fr.value,)
+    finally:
+        for q in (p, pv, ph):
+            lib.ketogpu_free(q)
+
+
+def host_lookup_via(snapshot, target, max_depth=DEPTH_ALL, type_id=TYPE_ANY):
+    """ketogpu_snapshot_lookup_via: (host_lookup_depth's ids, via, hops, frontier).  No GPU."""
+    return _host_via(snapshot, "ketogpu_snapshot_lookup_via", target, type_id, max_depth)
+
+
+def host_subjects_via(snapshot, root, max_depth=DEPTH_ALL, cls=TYPE_ANY):
+    """ketogpu_snapshot_subjects_via: (host_subjects_depth's ids, via, hops, frontier).  No GPU."""
+    return _host_via(snapshot, "ketogpu_snapshot_subjects_via", root, cls, max_depth)
+
+
+class _HostVia:
+    """the via calls of a CPU twin over self._via_members(x, k, filter_id) -> (ascending ids,
+    via, hops, frontier), laid out as the device calls lay their results out"""
+
+    def _via_all(self, ids, max_depth, filter_id):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        depth = depth_array(max_depth, len(ids))
+        n_nodes = self.snapshot.stats()["num_nodes"]
+        empty = np.zeros(0, dtype=np.uint32)
+        lists, frontier = [], np.zeros(len(ids), dtype=np.uint64)
+        for i, x in enumerate(ids):
+            if x >= n_nodes and x != L.NODE_NONE:
+                lists.append(None)
+            elif x == L.NODE_NONE:
+                lists.append((empty, empty, empty))
+            else:
+                m = self._via_members(int(x), DEPTH_ALL if depth is None else int(depth[i]), filter_id)
+                lists.append(m[:3])
+                frontier[i] = m[3]
+        return lists, frontier
+
+    def _ids_via_raw(self, ids, max_depth, filter_id=TYPE_ANY, capacity=0):
+        lists, frontier = self._via_all(ids, max_depth, filter_id)
+        out, begin, count, needed = _host_cursor([m if m is None else m[0] for m in lists], capacity)
+        via, hops = np.zeros(int(capacity), dtype=np.uint32), np.zeros(int(capacity), dtype=np.uint32)
+        for m, b, c in zip(lists, begin, count):
+            if m is not None and b != TRUNCATED:
+                via[int(b):int(b) + int(c)], hops[int(b):int(b) + int(c)] = m[1], m[2]
+        return out, via, hops, begin, count, frontier, needed
+
+    def _page_via_raw(self, ids, max_depth, from_ids=None, filter_id=TYPE_ANY, limit=100):
+        lists, frontier = self._via_all(ids, max_depth, filter_id)
+        invalid = [m is None for m in lists]
+        out, returned, count, remaining = _host_pages([m if m is None else m[0] for m in lists], invalid, from_ids,
+                                                      limit)
+        via, hops = np.zeros_like(out), np.zeros_like(out)
+        for i, m in enumerate(lists):
+            if m is None:
+                continue
+            k = int(np.searchsorted(m[0], 0 if from_ids is None else from_ids[i], side="left"))
+            r = int(returned[i])
+            via[i, :r], hops[i, :r] = m[1][k:k + r], m[2][k:k + r]
+        return out, via, hops, returned, count, remaining, frontier
+
+
+class _ObjectsVia:
+    """the object lists that say why over self.lookup_via_raw and self.snapshot"""
+
+    def lookup_via(self, targets, max_depth=None, type_id=TYPE_ANY, capacity=None):
+        """-> (per target (ids ascending, via, hops), frontier): lookup_depth's lists with, for
+        every member, the node whose reverse row it was first seen in (an entry of the member's
+        own row, one hop nearer the target) and its hop count.  Truncated lists are issued again."""
+        return _via_lists(lambda t, d, c: self.lookup_via_raw(t, d, type_id, c), targets, max_depth, capacity)
+
+    def list_objects_via_batch(self, namespace, relation, subjects, max_depth=None):
+        """per subject: (object name, via, hops) for the objects o with
+        Check(namespace:o#relation@subject), sorted by name; via is the subject (a subject set,
+        or the subject itself at one hop) that o holds directly on its way to the subject"""
+        ty = self.snapshot.type_id(namespace, relation)
+        targets = resolve_subjects(self.snapshot, list(subjects))
+        if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
+            return [[] for _ in targets]
+        lists, _ = self.lookup_via(targets, max_depth, ty)
+        return [sorted(((self.snapshot.node_info(int(v))["id"], self.snapshot.describe(int(w)), int(h))
+                        for v, w, h in zip(*m)), key=lambda e: e[0]) for m in lists]
+
+
+class _SubjectsVia:
+    """the subject lists that say why over self.subject_via_raw and self.snapshot"""
+
+    def subject_via(self, roots, max_depth=None, cls=TYPE_ANY, capacity=None):
+        """-> (per root (ids ascending, via, hops), frontier): subject_depth's lists with, for
+        every member, the node whose row holds it (one hop nearer the root) and its hop count.
+        Truncated lists are issued again."""
+        return _via_lists(lambda r, d, c: self.subject_via_raw(r, d, cls, c), roots, max_depth, capacity)
+
+    def list_subjects_via_batch(self, roots, kind="ids", max_depth=None):
+        """per (namespace, object, relation) root: (subject, via, hops) in list_subjects_batch's
+        order; via is the subject set whose tuple names the subject"""
+        roots = list(roots)
+        cls = _class_of_kind(self.snapshot, kind)
+        ids = resolve_roots(self.snapshot, roots)
+        if cls == TYPE_NONE:
+            return [[] for _ in roots]
+        lists, _ = self.subject_via(ids, max_depth, cls)
+        res = []
+        for m in lists:
+            why = {self.snapshot.describe(int(v)): (self.snapshot.describe(int(w)), int(h)) for v, w, h in zip(*m)}
+            res.append([(sub,) + why[sub] for sub in _subjects_of(self.snapshot, m[0])])
+        return res
 
 
 # ---- combined listings: M(a) op M(b) (include/ketogpu.h "combined listings", DESIGN.md
@@ -691,6 +900,46 @@ class _Handle:
                                         remaining.ctypes.data, frontier.ctypes.data))
         return out[:n], returned[:n], count[:n], remaining[:n], frontier[:n]
 
+    # ---- listings that say why
+    def via_stats(self):
+        return self._stats(L.ViaStats(), "via_stats_get")
+
+    def _ids_via_raw(self, requests, max_depth, filter_id=TYPE_ANY, capacity=0, want_via=True, want_hops=True):
+        """one ketogpu_<ABI>_ids_via call -> (out, via, hops, begin, count, frontier, needed):
+        _ids_depth_raw's results with via[k] and hops[k] belonging to out[k].  want_via /
+        want_hops False: that array is passed as NULL and comes back as None"""
+        requests = np.ascontiguousarray(requests, dtype=np.uint32)
+        n = len(requests)
+        depth = depth_array(max_depth, n)
+        cap = int(capacity)
+        out = np.empty(max(cap, 1), dtype=np.uint32)
+        via = np.empty(max(cap, 1), dtype=np.uint32) if want_via else None
+        hops = np.empty(max(cap, 1), dtype=np.uint32) if want_hops else None
+        begin = np.empty(max(n, 1), dtype=np.uint64)
+        count = np.empty(max(n, 1), dtype=np.uint64)
+        frontier = np.zeros(max(n, 1), dtype=np.uint64)
+        needed = C.c_uint64()
+        ptr = lambda a: a.ctypes.data if cap and a is not None else None
+        L.check(self._abi("ids_via")(self.h, requests.ctypes.data, None if depth is None else depth.ctypes.data, n,
+                                     int(filter_id), ptr(out), ptr(via), ptr(hops), cap, begin.ctypes.data,
+                                     count.ctypes.data, frontier.ctypes.data, C.byref(needed)))
+        cut = lambda a: None if a is None else a[:cap]
+        return out[:cap], cut(via), cut(hops), begin[:n], count[:n], frontier[:n], needed.value
+
+    def _page_via_raw(self, requests, max_depth, from_ids=None, filter_id=TYPE_ANY, limit=100):
+        """one ketogpu_<ABI>_page_via call -> (out[n, limit], via[n, limit], hops[n, limit],
+        returned, count, remaining, frontier): _page_depth_raw's results with via and hops at the
+        same stride, valid for the first returned[i] entries of row i"""
+        requests, lo, n, limit, out, returned, count, remaining = _page_args(requests, from_ids, limit)
+        depth = depth_array(max_depth, n)
+        via, hops = np.empty_like(out), np.empty_like(out)
+        frontier = np.zeros(max(n, 1), dtype=np.uint64)
+        L.check(self._abi("page_via")(self.h, requests.ctypes.data, None if depth is None else depth.ctypes.data,
+                                      None if lo is None else lo.ctypes.data, n, int(filter_id), limit,
+                                      out.ctypes.data, via.ctypes.data, hops.ctypes.data, returned.ctypes.data,
+                                      count.ctypes.data, remaining.ctypes.data, frontier.ctypes.data))
+        return out[:n], via[:n], hops[:n], returned[:n], count[:n], remaining[:n], frontier[:n]
+
     # ---- combined listings
     def combine_stats(self):
         return self._stats(L.CombineStats(), "combine_stats_get")
@@ -712,9 +961,17 @@ class _Handle:
         return out[:n], returned[:n], count[:n], remaining[:n]
 
 
-class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth):
+class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth, _ObjectsVia):
     """device handle over a snapshot's reverse rows"""
     ABI, OPTS, STATS = "lookup", L.LookupOpts, L.LookupStats
+
+    def lookup_via_raw(self, targets, max_depth=None, type_id=TYPE_ANY, capacity=0, **want):
+        """one ketogpu_lookup_ids_via call (_ids_via_raw)"""
+        return self._ids_via_raw(targets, max_depth, type_id, capacity, **want)
+
+    def lookup_via_page_raw(self, targets, max_depth=None, from_ids=None, type_id=TYPE_ANY, limit=100):
+        """one ketogpu_lookup_page_via call (_page_via_raw)"""
+        return self._page_via_raw(targets, max_depth, from_ids, type_id, limit)
 
     def lookup_depth_raw(self, targets, max_depth, type_id=TYPE_ANY, capacity=0):
         """one ketogpu_lookup_ids_depth call (_ids_depth_raw)"""
@@ -756,9 +1013,12 @@ class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth):
     def _objects(self, ids):
         return sorted(self.snapshot.node_info(int(v))["id"] for v in ids)
 
-    def list_objects_batch(self, namespace, relation, subjects, max_depth=None):
+    def list_objects_batch(self, namespace, relation, subjects, max_depth=None, with_via=False):
         """per subject: the sorted object names o with Check(namespace:o#relation@subject); with
-        max_depth, those within that many hops (list_objects_depth_batch's lists)"""
+        max_depth, those within that many hops (list_objects_depth_batch's lists); with_via:
+        (name, via, hops) instead of names (list_objects_via_batch)"""
+        if with_via:
+            return self.list_objects_via_batch(namespace, relation, subjects, max_depth)
         if max_depth is not None:
             return self.list_objects_depth_batch(namespace, relation, subjects, max_depth)[0]
         ty = self.snapshot.type_id(namespace, relation)
@@ -767,8 +1027,8 @@ class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth):
             return [[] for _ in targets]
         return [self._objects(ids) for ids in self.lookup_ids(targets, ty)]
 
-    def ListObjects(self, namespace, relation, subject, max_depth=None):
-        return self.list_objects_batch(namespace, relation, [subject], max_depth)[0]
+    def ListObjects(self, namespace, relation, subject, max_depth=None, with_via=False):
+        return self.list_objects_batch(namespace, relation, [subject], max_depth, with_via)[0]
 
 
 def host_list_objects(snapshot, namespace, relation, subject):
@@ -780,13 +1040,23 @@ def host_list_objects(snapshot, namespace, relation, subject):
     return sorted(snapshot.node_info(int(v))["id"] for v in host_lookup(snapshot, t, ty))
 
 
-class HostLookup(_ObjectPages, _Paths, _HostCombine, _ObjectsCombined, _HostDepth, _ObjectsDepth):
-    """Lookup's paged, path, combined and depth calls on the CPU: host_lookup's ascending lists,
-    sliced or combined, host_path's paths laid out as the device call lays them out, and
-    host_lookup_depth's lists"""
+class HostLookup(_ObjectPages, _Paths, _HostCombine, _ObjectsCombined, _HostDepth, _ObjectsDepth, _HostVia,
+                 _ObjectsVia):
+    """Lookup's paged, path, combined, depth and via calls on the CPU: host_lookup's ascending
+    lists, sliced or combined, host_path's paths laid out as the device call lays them out,
+    host_lookup_depth's lists and host_lookup_via's"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def _via_members(self, x, k, type_id):
+        return host_lookup_via(self.snapshot, x, k, type_id)
+
+    def lookup_via_raw(self, targets, max_depth=None, type_id=TYPE_ANY, capacity=0):
+        return self._ids_via_raw(targets, max_depth, type_id, capacity)
+
+    def lookup_via_page_raw(self, targets, max_depth=None, from_ids=None, type_id=TYPE_ANY, limit=100):
+        return self._page_via_raw(targets, max_depth, from_ids, type_id, limit)
 
     def _depth_members(self, x, k, type_id):
         if x == L.NODE_NONE:
@@ -882,9 +1152,17 @@ def _subjects_of(snapshot, ids):
     return users + sets
 
 
-class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth):
+class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth, _SubjectsVia):
     """device handle over a snapshot's forward rows"""
     ABI, OPTS, STATS = "subjects", L.SubjectsOpts, L.SubjectsStats
+
+    def subject_via_raw(self, roots, max_depth=None, cls=TYPE_ANY, capacity=0, **want):
+        """one ketogpu_subjects_ids_via call (_ids_via_raw)"""
+        return self._ids_via_raw(roots, max_depth, cls, capacity, **want)
+
+    def subject_via_page_raw(self, roots, max_depth=None, from_ids=None, cls=TYPE_ANY, limit=100):
+        """one ketogpu_subjects_page_via call (_page_via_raw)"""
+        return self._page_via_raw(roots, max_depth, from_ids, cls, limit)
 
     def subject_depth_raw(self, roots, max_depth, cls=TYPE_ANY, capacity=0):
         """one ketogpu_subjects_ids_depth call (_ids_depth_raw)"""
@@ -912,11 +1190,14 @@ class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth):
         return self._page_raw(roots, from_ids, cls, limit)
 
     # ---- names
-    def list_subjects_batch(self, roots, kind="ids", max_depth=None):
+    def list_subjects_batch(self, roots, kind="ids", max_depth=None, with_via=False):
         """per (namespace, object, relation) root: the subjects s with Check(root@s), SubjectIDs
         then SubjectSets, each sorted.  kind: "ids" (subject ids only), "any", or a
         (namespace, relation) pair (subject sets of that type; an unknown pair lists nothing).
-        With max_depth: those within that many hops (list_subjects_depth_batch's lists)"""
+        With max_depth: those within that many hops (list_subjects_depth_batch's lists); with_via:
+        (subject, via, hops) instead of subjects (list_subjects_via_batch)"""
+        if with_via:
+            return self.list_subjects_via_batch(roots, kind, max_depth)
         if max_depth is not None:
             return self.list_subjects_depth_batch(roots, max_depth, kind)[0]
         roots = list(roots)
@@ -926,16 +1207,26 @@ class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth):
             return [[] for _ in roots]
         return [_subjects_of(self.snapshot, v) for v in self.subject_ids(ids, cls)]
 
-    def ListSubjects(self, namespace, object, relation, kind="ids", max_depth=None):
-        return self.list_subjects_batch([(namespace, object, relation)], kind, max_depth)[0]
+    def ListSubjects(self, namespace, object, relation, kind="ids", max_depth=None, with_via=False):
+        return self.list_subjects_batch([(namespace, object, relation)], kind, max_depth, with_via)[0]
 
 
-class HostSubjects(_SubjectPages, _HostCombine, _SubjectsCombined, _HostDepth, _SubjectsDepth):
-    """Subjects' paged, combined and depth calls on the CPU: host_subjects' ascending lists,
-    sliced or combined, and host_subjects_depth's lists"""
+class HostSubjects(_SubjectPages, _HostCombine, _SubjectsCombined, _HostDepth, _SubjectsDepth, _HostVia,
+                   _SubjectsVia):
+    """Subjects' paged, combined, depth and via calls on the CPU: host_subjects' ascending lists,
+    sliced or combined, host_subjects_depth's lists and host_subjects_via's"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def _via_members(self, x, k, cls):
+        return host_subjects_via(self.snapshot, x, k, cls)
+
+    def subject_via_raw(self, roots, max_depth=None, cls=TYPE_ANY, capacity=0):
+        return self._ids_via_raw(roots, max_depth, cls, capacity)
+
+    def subject_via_page_raw(self, roots, max_depth=None, from_ids=None, cls=TYPE_ANY, limit=100):
+        return self._page_via_raw(roots, max_depth, from_ids, cls, limit)
 
     def _depth_members(self, x, k, cls):
         if x == L.NODE_NONE:
@@ -972,4 +1263,5 @@ __all__ = ["Lookup", "host_lookup", "host_list_objects", "resolve_subjects", "Su
            "host_list_subjects", "resolve_roots", "TYPE_ANY", "TYPE_NONE", "CLASS_SUBJECT_ID", "CLASS_UNTYPED_SET",
            "TRUNCATED", "INVALID", "SubjectID", "SubjectSet", "HostLookup", "HostSubjects", "PAGE_LIMIT_MAX",
            "PAGE_INVALID", "parse_page_token", "check_page_size", "next_page_token", "host_path", "OP_AND", "OP_ANDNOT",
-           "OP_OR", "op_id", "DEPTH_ALL", "host_lookup_depth", "host_subjects_depth", "depth_array"]
+           "OP_OR", "op_id", "DEPTH_ALL", "host_lookup_depth", "host_subjects_depth", "depth_array", "host_lookup_via",
+           "host_subjects_via", "grant_chain"]
