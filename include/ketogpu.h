@@ -1402,6 +1402,57 @@ int ketogpu_subjects_page_via(ketogpu_subjects *h, const uint32_t *roots, const 
                               uint32_t *hops /* n * limit words or NULL */, uint32_t *returned, uint64_t *count,
                               uint64_t *remaining, uint64_t *frontier);
 
+/* ------------------------------------------------- listing handles and in-place writes
+ * A listing handle over a KETOGPU_BUILD_WRITABLE snapshot follows ketogpu_snapshot_write by
+ * replaying the snapshot's patch log: the rows a write rewrote are packed on the host, copied
+ * once and scattered by one kernel ahead of the call's own, so the first call after a write
+ * costs what the write touched.  The lookup handle overwrites reverse rows where they lie;
+ * the subjects handle keeps every forward row in an arena with the host's growth rule
+ * (capacity len + len / 4 + 4) and moves a row that outgrew its capacity to the arena's tail.
+ * The handle uploads everything again (a FULL upload) at creation, when the log was trimmed
+ * below its position, when the backlog's rows exceed a quarter of a full upload's bytes, when
+ * the arena's tail is exhausted or its garbage passes max(num_edges / 4, 2^20) words (a
+ * compaction), and on every version change under KETOGPU_LIST_REFRESH=full (env, read at
+ * *_new).  KETOGPU_LIST_ARENA_SLACK (env, words) sets the arena's tail headroom.  The
+ * subjects handle's tier-2 bitmaps span num_nodes rounded up to a multiple of
+ * KETOGPU_LIST_BOUND_STEP (env, default 32768), so that a new subject seldom moves the span:
+ * when it does, tier 2's state is dropped and the next tier-2 call allocates it again.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+typedef struct {
+    uint64_t full_uploads;      /* 1 at creation, +1 per refresh served by a full upload      */
+    uint64_t patched_refreshes; /* refreshes served by the patch kernel                       */
+    uint64_t rows_patched;      /* rows the patch kernel rewrote                              */
+    uint64_t rows_moved;        /* ... of them moved to the arena's tail (subjects handle)    */
+    uint64_t words_uploaded;    /* 4-byte words copied to the device by patched refreshes     */
+    uint64_t compactions;       /* full uploads because the arena needed compaction           */
+    uint64_t fallbacks_trimmed; /* full uploads because the log was trimmed below the handle  */
+    uint64_t fallbacks_backlog; /* full uploads because the backlog outweighed them           */
+    double last_refresh_ms;     /* host wall time of the last refresh that moved the version  */
+} ketogpu_list_refresh_stats;
+int ketogpu_lookup_refresh_stats_get(const ketogpu_lookup *l, ketogpu_list_refresh_stats *out);
+int ketogpu_subjects_refresh_stats_get(const ketogpu_subjects *h, ketogpu_list_refresh_stats *out);
+
+/* A host-side reader of a writable snapshot's patch log, for tests and integrators that keep
+ * state of their own per row.  An entry names a row a committed write rewrote:
+ * KETOGPU_PATCH_FORWARD_INTERIOR the interior successors of an expandable node (the check
+ * engine's forward row), KETOGPU_PATCH_REVERSE the reverse row of a node (what
+ * ketogpu_snapshot_lookup walks), KETOGPU_PATCH_FORWARD_FULL the full forward row of an
+ * expandable node (what ketogpu_snapshot_subjects walks).  A reader starts at the log's end,
+ * registers like an engine (the log is kept from its position on until it is freed) and
+ * advances by what it reads: _next copies up to `capacity` entries, in write order, and sets
+ * *n to their number (0: nothing pending).  A refused write logs nothing.  On a snapshot that
+ * is not writable the log stays empty. */
+#define KETOGPU_PATCH_FORWARD_INTERIOR 0
+#define KETOGPU_PATCH_REVERSE 1
+#define KETOGPU_PATCH_FORWARD_FULL 2
+typedef struct ketogpu_patch_reader ketogpu_patch_reader;
+int ketogpu_patch_reader_new(const ketogpu_snapshot *s, ketogpu_patch_reader **out);
+int ketogpu_patch_reader_next(ketogpu_patch_reader *r, uint8_t *kinds, uint32_t *nodes, size_t capacity, size_t *n);
+/* the reader's absolute position and the range of the log the snapshot still keeps (each may be null) */
+int ketogpu_patch_reader_position(const ketogpu_patch_reader *r, uint64_t *position, uint64_t *log_begin,
+                                  uint64_t *log_end);
+void ketogpu_patch_reader_free(ketogpu_patch_reader *r);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

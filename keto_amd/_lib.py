@@ -384,6 +384,19 @@ class ViaStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# include/ketogpu.h listing handles and in-place writes
+class ListRefreshStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "full_uploads", "patched_refreshes", "rows_patched", "rows_moved", "words_uploaded", "compactions",
+        "fallbacks_trimmed", "fallbacks_backlog")] + [("last_refresh_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+PATCH_FORWARD_INTERIOR, PATCH_REVERSE, PATCH_FORWARD_FULL = 0, 1, 2
+
+
 # every symbol declared in include/ketogpu.h, with its ctypes signature
 vp, i32, u32, sz = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t
 SIGNATURES = {
@@ -538,6 +551,13 @@ SIGNATURES = {
     "ketogpu_subjects_ids_depth": (C.c_int, [vp, vp, vp, sz, u32, vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]),
     "ketogpu_lookup_page_depth": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp]),
     "ketogpu_subjects_page_depth": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp]),
+    "ketogpu_lookup_refresh_stats_get": (C.c_int, [vp, C.POINTER(ListRefreshStats)]),
+    "ketogpu_subjects_refresh_stats_get": (C.c_int, [vp, C.POINTER(ListRefreshStats)]),
+    "ketogpu_patch_reader_new": (C.c_int, [vp, C.POINTER(vp)]),
+    "ketogpu_patch_reader_next": (C.c_int, [vp, vp, vp, sz, C.POINTER(sz)]),
+    "ketogpu_patch_reader_position": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_uint64)]),
+    "ketogpu_patch_reader_free": (None, [vp]),
     "ketogpu_lookup_via_stats_get": (C.c_int, [vp, C.POINTER(ViaStats)]),
     "ketogpu_subjects_via_stats_get": (C.c_int, [vp, C.POINTER(ViaStats)]),
     "ketogpu_snapshot_lookup_via": (C.c_int, [vp, u32, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),

@@ -50,7 +50,16 @@ struct Rows {
     const uint32_t *col;
     const uint32_t *filter_key;  // per node, what the member filter compares: object type or class
     uint32_t N, Nx, Ni;
+    // null: row v ends at off[v + 1] (a dense CSR).  Else row v is col[off[v] .. end[v]): rows
+    // that can grow lie in an arena with free words behind each (hip_host.hpp "arena")
+    const uint64_t *end = nullptr;
 };
+
+// the entries of row v are col[b .. e).  The branch is on a kernel argument: uniform
+__device__ __forceinline__ void row_bounds(const Rows &g, uint32_t v, uint64_t &b, uint64_t &e) {
+    b = g.off[v];
+    e = g.end ? g.end[v] : g.off[v + 1];
+}
 
 struct ListOut {
     uint32_t *out;
@@ -102,7 +111,8 @@ __device__ __forceinline__ bool tier1_closure(const Rows &g, uint32_t bound, uin
     uint32_t size = 0, head = 0, tail = 0;  // wave-uniform
     bool over = false;
     for (;;) {
-        const uint64_t b = g.off[v], e = g.off[v + 1];
+        uint64_t b, e;
+        row_bounds(g, v, b, e);
         for (uint64_t base = b; base < e && !over; base += 64) {
             const uint64_t j = base + lane;
             const uint32_t u = j < e ? g.col[j] : kEmpty;
@@ -160,7 +170,8 @@ __device__ __forceinline__ void tier2_closure(const Rows &g, uint32_t bound, uin
         if (u < g.Ni) wl[atomicAdd(s_tail, 1u)] = u;  // each interior node enters once: <= Ni entries
     };
     {  // the start's own row, by the whole workgroup
-        const uint64_t b = g.off[v0], e = g.off[v0 + 1];
+        uint64_t b, e;
+        row_bounds(g, v0, b, e);
         for (uint64_t j = b + tid; j < e; j += kT2Block) visit(g.col[j], v0);
     }
     __syncthreads();
@@ -170,7 +181,8 @@ __device__ __forceinline__ void tier2_closure(const Rows &g, uint32_t bound, uin
         __syncthreads();        // everyone has read s_tail and the stop condition before they move
         for (uint32_t k = lb + wave; k < le; k += nwaves) {
             const uint32_t v = wl[k];
-            const uint64_t b = g.off[v], e = g.off[v + 1];
+            uint64_t b, e;
+            row_bounds(g, v, b, e);
             for (uint64_t j = b + lane; j < e; j += 64) visit(g.col[j], v);
         }
         __syncthreads();  // the level is complete

@@ -82,7 +82,8 @@ __device__ __forceinline__ bool tier1_closure_pair(const Rows &g, uint32_t bound
     uint32_t size = 0, head = 0, tail = 0;  // wave-uniform
     bool over = false;
     for (;;) {
-        const uint64_t b = g.off[v], e = g.off[v + 1];
+        uint64_t b, e;
+        row_bounds(g, v, b, e);
         for (uint64_t base = b; base < e && !over; base += 64) {
             const uint64_t j = base + lane;
             const uint32_t u = j < e ? g.col[j] : kEmpty;

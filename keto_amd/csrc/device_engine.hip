@@ -5258,7 +5258,8 @@ struct ketogpu_engine {
         std::vector<uint32_t> fr, rr;
         for (uint64_t i = patch_pos; i < s.patch_end(); i++) {
             const Snapshot::Patch &pt = s.patches[i - s.patch_base];
-            (pt.rev ? rr : fr).push_back(pt.node);
+            if (pt.kind == KETOGPU_PATCH_FORWARD_FULL) continue;  // (the listing handles' rows, not the engine's)
+            (pt.kind == KETOGPU_PATCH_REVERSE ? rr : fr).push_back(pt.node);
         }
         for (auto *v : {&fr, &rr}) {
             std::sort(v->begin(), v->end());

@@ -2,8 +2,10 @@
 // HIP calls and launches, a device array that only grows, the C ABI's error guard, and
 // ListHandle: the state both handles carry, the drivers of their calls (tier 1, the read of the
 // overflow count, tier 2 in rounds of `slots`, the copies back) and the shared parts of their
-// ABI entry points.  A handle adds its graph struct, its upload, its launches (passed to the
-// drivers as callables) and its statistics.
+// ABI entry points, and how a handle follows in-place writes: the patched refresh (try_patch,
+// list_patch_kernel) with the full upload as its fallback.  A handle adds its graph struct, its
+// upload, what the patched refresh asks of it, its launches (passed to the drivers as callables)
+// and its statistics.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +13,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -59,6 +62,50 @@ struct DBuf {
         p = nullptr, cap = 0;
     }
 };
+
+// a pinned host array that only grows: the staging of a patched refresh
+template <class T>
+struct PBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    void need(size_t n) {
+        if (n <= cap && p) return;
+        drop();
+        void *q = nullptr;
+        n = std::max<size_t>(n + n / 2, 1024);
+        hipError_t e = hipHostMalloc(&q, n * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) throw Error(KETOGPU_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+        p = (T *)q, cap = n;
+    }
+    void drop() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr, cap = 0;
+    }
+};
+
+// One segment of a patched refresh, four words: where its words go, where they lie in the
+// staging array, how many there are, and (what << 32 | node).  kSegRow: a row copied into col
+// where it lies already; kSegRowBounds: ... with off[node] and end[node] rewritten (the arena);
+// kSegKeys: the filter keys of new nodes, copied into the key array.
+constexpr uint64_t kSegRow = 0, kSegRowBounds = 1, kSegKeys = 2;
+constexpr size_t kSegWords = 4;
+constexpr unsigned kPatchBlock = 256;
+
+// The scatter of a patched refresh: one workgroup per segment, grid-stride over the segments;
+// consecutive threads copy consecutive words.  The host has checked every segment against the
+// sizes of stage, col, off / end and key before the launch (ListHandle::try_patch).
+static __global__ __launch_bounds__(kPatchBlock) void list_patch_kernel(const uint64_t *seg, uint64_t nseg,
+                                                                        const uint32_t *stage, uint32_t *col,
+                                                                        uint64_t *off, uint64_t *end, uint32_t *key) {
+    for (uint64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const uint64_t dst = seg[kSegWords * s], src = seg[kSegWords * s + 1], len = seg[kSegWords * s + 2];
+        const uint64_t what = seg[kSegWords * s + 3] >> 32;
+        const uint32_t node = (uint32_t)seg[kSegWords * s + 3];
+        uint32_t *to = what == kSegKeys ? key : col;
+        for (uint64_t k = threadIdx.x; k < len; k += kPatchBlock) to[dst + k] = stage[src + k];
+        if (what == kSegRowBounds && threadIdx.x == 0) off[node] = dst, end[node] = dst + len;
+    }
+}
 
 template <class F>
 int guarded(F &&f) {
@@ -116,11 +163,46 @@ struct ListHandle {
     uint32_t bound = 0;                // the member bound the closures take: the bitmaps span it
     uint64_t bm_words = 0;
 
+    // ---- following in-place writes (DESIGN.md "Listing handles and writes").  A handle over a
+    // writable snapshot reads the snapshot's patch log from patch_pos on and rewrites the rows
+    // it names (try_patch); upload_rows is the fallback, and the only path otherwise.
+    ketogpu_list_refresh_stats rst{};
+    bool refresh_full = false;    // KETOGPU_LIST_REFRESH=full: every version change uploads everything
+    uint64_t slack_knob = ~0ull;  // KETOGPU_LIST_ARENA_SLACK: the arena's tail headroom in words (~0: the default)
+    // A handle whose bound follows N (subjects) sizes tier 2's bitmaps for N rounded up to a
+    // multiple of this (KETOGPU_LIST_BOUND_STEP; at most 1024 more zero words per bitmap), so that
+    // a write that adds a subject seldom moves the bound: dropping tier 2's state costs the next
+    // tier-2 call its allocation and zeroing, which is proportional to slots x N
+    uint32_t bound_step = 32768;
+    uint32_t bound_above(uint32_t n) const {
+        return (uint32_t)std::min<uint64_t>(((uint64_t)n + bound_step - 1) / bound_step * bound_step, 0xfffffffeu);
+    }
+    bool registered = false;      // a reader of the log, at patch_pos
+    uint64_t patch_pos = 0;
+    uint64_t n_rows = 0, col_words = 0, key_words = 0;  // the device arrays' sizes: segments are checked against them
+    uint64_t full_bytes = 0;                            // what the last full upload copied
+    // the arena (subjects handle, writable snapshots): row v lies at m_begin[v] with room for
+    // m_cap[v] words; rows that outgrow it move to arena_tail, and their old words are garbage
+    bool arena = false;
+    std::vector<uint64_t> m_begin;
+    std::vector<uint32_t> m_cap;
+    uint64_t arena_tail = 0, arena_garbage = 0;
+    DBuf<uint64_t> d_end, d_seg;
+    DBuf<uint32_t> d_stage;
+    PBuf<uint32_t> h_stage;  // the patched rows back to back, then the new nodes' keys
+    PBuf<uint64_t> h_seg;
+    std::vector<uint32_t> patch_nodes;  // (kept between refreshes: no allocation per write)
+
     explicit ListHandle(const char *subsystem) : what(subsystem) {}
 
     ~ListHandle() {
+        if (registered && link) {  // (a snapshot freed first has cleared the link: nothing of it is touched)
+            std::lock_guard<std::mutex> lk(link->mu);
+            if (link->snap) link->snap->reader_gone(this);
+        }
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+        d_end.drop(), d_seg.drop(), d_stage.drop(), h_stage.drop(), h_seg.drop();
         d_off.drop(), d_col.drop(), d_label.drop(), d_req.drop(), d_req2.drop(), d_ovf.drop(), d_out.drop();
         d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop(), d_bm.drop(), d_wl.drop();
         d_aux.drop(), d_bm2.drop(), d_front.drop(), d_via.drop(), d_hops.drop(), d_viast.drop();
@@ -130,29 +212,160 @@ struct ListHandle {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 
-    // one version's rows and labels to the device; true when (bound, Ni) moved, and tier 2's
-    // state, which follows the sizes, was dropped
-    bool upload_rows(const Snapshot &s, const uint64_t *off, size_t n_off, const uint32_t *col, size_t n_col,
-                     const uint32_t *label, size_t n_label, uint32_t new_bound) {
-        d_off.need(n_off), d_col.need(n_col), d_label.need(n_label);
+    // tier 2's state follows (bound, Ni): dropped when they move
+    void drop_tier2() {
+        slots = 0, slot_max = 0, d_bm.drop(), d_wl.drop(), d_aux.drop();
+        pair_slots = 0, pair_slot_max = 0, d_bm2.drop();
+        via_slots = 0, via_slot_max = 0, d_viast.drop();
+    }
+
+    // one version's rows and labels to the device, all of them: a full upload.  `end`: the rows'
+    // ends when they lie in an arena (null: a dense CSR); col_room and label_room: the words
+    // to allocate, at least what is copied.  The handle then stands at the log's end.  True when
+    // (bound, Ni) moved, and tier 2's state, which follows the sizes, was dropped
+    bool upload_rows(const Snapshot &s, const uint64_t *off, const uint64_t *end, size_t n_off, const uint32_t *col,
+                     size_t n_col, size_t col_room, const uint32_t *label, size_t n_label, size_t label_room,
+                     uint32_t new_bound) {
+        col_room = std::max(col_room, n_col), label_room = std::max(label_room, n_label);
+        d_off.need(n_off), d_col.need(col_room), d_label.need(label_room);
+        if (end) d_end.need(n_off);
         HIP_CHECK(hipMemcpyAsync(d_off.p, off, n_off * 8, hipMemcpyHostToDevice, stream));
+        if (end) HIP_CHECK(hipMemcpyAsync(d_end.p, end, (n_off - 1) * 8, hipMemcpyHostToDevice, stream));
         if (n_col) HIP_CHECK(hipMemcpyAsync(d_col.p, col, n_col * 4, hipMemcpyHostToDevice, stream));
         if (n_label) HIP_CHECK(hipMemcpyAsync(d_label.p, label, n_label * 4, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         const bool moved = new_bound != bound || s.Ni != g.Ni;
-        if (moved) slots = 0, slot_max = 0, d_bm.drop(), d_wl.drop(), d_aux.drop();
-        if (moved) pair_slots = 0, pair_slot_max = 0, d_bm2.drop();
-        if (moved) via_slots = 0, via_slot_max = 0, d_viast.drop();
-        g = closure::Rows{d_off.p, d_col.p, d_label.p, s.N, s.Nx, s.Ni};
+        if (moved) drop_tier2();
+        g = closure::Rows{d_off.p, d_col.p, d_label.p, s.N, s.Nx, s.Ni, end ? d_end.p : nullptr};
         bound = new_bound, bm_words = ((uint64_t)bound + 31) / 32;
         version = s.version;
+        n_rows = n_off - 1, col_words = col_room, key_words = label_room;
+        full_bytes = (uint64_t)n_off * 8 * (end ? 2 : 1) + (uint64_t)n_col * 4 + (uint64_t)n_label * 4;
+        rst.full_uploads++;
+        if (s.writable && !refresh_full) {  // what the log holds so far is in these rows
+            patch_pos = s.patch_end();
+            s.reader_at(this, patch_pos);
+            registered = true;
+        }
         return moved;
     }
 
-    // the rows of the snapshot's current version, uploaded again (by the handle's
-    // upload(snapshot)) if a write moved it
-    template <class Upload>
-    void refresh(Upload &&upload) {
+    // The patched refresh (caller holds the snapshot's shared lock): the rows of H::kPatchKind
+    // that the log names from patch_pos on, packed into the pinned staging array from the
+    // snapshot's current host rows, copied once with their segment table and scattered by
+    // list_patch_kernel on the handle's stream, ahead of the call's kernels.  Host and device
+    // work is O(the patched rows' entries + new nodes).  False: the handle must upload
+    // everything instead (counted with its reason); nothing was changed then.
+    // H supplies
+    //   host_row(s, v, p, len, at)  the entries of row v, and where the row lies on the device
+    //                               when that never moves (no arena)
+    //   host_keys(s)                the filter keys of all N nodes when new nodes have one, else null
+    //   bound_of(s)                 the member bound
+    //   moved()                     (bound, Ni) moved: the handle's own tier-2 state goes too
+    template <class H>
+    bool try_patch(const Snapshot &s, H &h) {
+        if (!s.writable || refresh_full || !registered) return false;
+        if (patch_pos < s.patch_base) {
+            rst.fallbacks_trimmed++;
+            return false;
+        }
+        patch_nodes.clear();
+        for (uint64_t i = patch_pos; i < s.patch_end(); i++) {
+            const Snapshot::Patch &pt = s.patches[i - s.patch_base];
+            if (pt.kind == H::kPatchKind) patch_nodes.push_back(pt.node);
+        }
+        std::sort(patch_nodes.begin(), patch_nodes.end());
+        patch_nodes.erase(std::unique(patch_nodes.begin(), patch_nodes.end()), patch_nodes.end());
+        const uint32_t *keys = h.host_keys(s);
+        if (s.N < g.N) throw Error(KETOGPU_EINVAL, what + ": the snapshot lost nodes in place");
+        const uint64_t new_keys = keys ? s.N - g.N : 0;
+        if (new_keys && g.N + new_keys > key_words) throw Error(KETOGPU_EINVAL, what + ": more nodes than the key array has room for");
+        // the plan: where every row goes.  Nothing of the handle is changed before it is complete
+        struct Move {
+            uint32_t v, cap;
+            uint64_t at;
+        };
+        std::vector<Move> moves;
+        uint64_t words = 0, tail = arena_tail, garbage = arena_garbage;
+        const size_t nseg = patch_nodes.size() + (new_keys ? 1 : 0);
+        h_seg.need(kSegWords * std::max<size_t>(nseg, 1));
+        for (size_t k = 0; k < patch_nodes.size(); k++) {
+            const uint32_t v = patch_nodes[k];
+            if (v >= n_rows) throw Error(KETOGPU_EINVAL, what + ": the log names a row the handle does not have");
+            const uint32_t *p;
+            uint64_t len, at;
+            h.host_row(s, v, p, len, at);
+            if (arena) {
+                at = m_begin[v];
+                if (len > m_cap[v]) {  // outgrown: to the tail, with the host's growth rule
+                    const uint64_t cap = len + len / 4 + 4;
+                    if (cap > 0xffffffffull || tail + cap > col_words) {
+                        rst.compactions++;  // the tail is exhausted
+                        return false;
+                    }
+                    at = tail, tail += cap, garbage += m_cap[v];
+                    moves.push_back({v, (uint32_t)cap, at});
+                }
+            }
+            if (at + len > col_words) throw Error(KETOGPU_EINVAL, what + ": a patched row ends outside the rows");
+            uint64_t *sg = h_seg.p + kSegWords * k;
+            sg[0] = at, sg[1] = words, sg[2] = len, sg[3] = (arena ? kSegRowBounds : kSegRow) << 32 | v;
+            words += len;
+        }
+        if (arena && garbage > std::max<uint64_t>(s.stats.num_edges / 4, 1ull << 20)) {
+            rst.compactions++;
+            return false;
+        }
+        if (words * 4 > full_bytes / 4) {
+            rst.fallbacks_backlog++;
+            return false;
+        }
+        // (the staging arrays are free: every call ends with the stream drained, and an earlier
+        // call that threw is waited for here)
+        HIP_CHECK(hipStreamSynchronize(stream));
+        h_stage.need(std::max<uint64_t>(words + new_keys, 1));
+        for (size_t k = 0; k < patch_nodes.size(); k++) {
+            const uint32_t *p;
+            uint64_t len, at;
+            h.host_row(s, patch_nodes[k], p, len, at);
+            if (len) memcpy(h_stage.p + h_seg.p[kSegWords * k + 1], p, len * 4);
+        }
+        if (new_keys) {
+            uint64_t *sg = h_seg.p + kSegWords * patch_nodes.size();
+            sg[0] = g.N, sg[1] = words, sg[2] = new_keys, sg[3] = kSegKeys << 32;
+            memcpy(h_stage.p + words, keys + g.N, new_keys * 4);
+        }
+        if (nseg) {
+            d_stage.need(words + new_keys), d_seg.need(kSegWords * nseg);
+            if (words + new_keys)
+                HIP_CHECK(hipMemcpyAsync(d_stage.p, h_stage.p, (words + new_keys) * 4, hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(d_seg.p, h_seg.p, kSegWords * nseg * 8, hipMemcpyHostToDevice, stream));
+            KLAUNCH(list_patch_kernel, dim3((unsigned)std::min<size_t>(nseg, 4096)), dim3(kPatchBlock), 0, stream, d_seg.p,
+                    (uint64_t)nseg, d_stage.p, d_col.p, d_off.p, d_end.p, d_label.p);
+        }
+        for (const Move &m : moves) m_begin[m.v] = m.at, m_cap[m.v] = m.cap;
+        arena_tail = tail, arena_garbage = garbage;
+        g.N = s.N;
+        const uint32_t new_bound = h.bound_of(s);
+        if (new_bound != bound) {  // a new subject raised N: as upload_rows does
+            drop_tier2();
+            h.moved();
+            bound = new_bound, bm_words = ((uint64_t)bound + 31) / 32;
+        }
+        patch_pos = s.patch_end();
+        s.reader_at(this, patch_pos);
+        version = s.version;
+        rst.patched_refreshes++;
+        rst.rows_patched += patch_nodes.size();
+        rst.rows_moved += moves.size();
+        rst.words_uploaded += words + new_keys + 2 * kSegWords * nseg;
+        return true;
+    }
+
+    // the rows of the snapshot's current version: patched if a write moved it, or uploaded
+    // again by the handle's upload(snapshot)
+    template <class H>
+    void refresh(H &h) {
         // (the link's lock is not held together with the snapshot's: a snapshot is not
         // freed while a call on it runs, only before or after)
         const Snapshot *sp;
@@ -162,7 +375,14 @@ struct ListHandle {
         }
         if (!sp) throw Error(KETOGPU_EINVAL, what + ": the snapshot was freed");
         std::shared_lock<std::shared_mutex> rd(sp->mu);
-        if (sp->version != version) upload(*sp);
+        if (sp->version == version) return;
+        const auto r0 = std::chrono::steady_clock::now();
+        if (try_patch(*sp, h))
+            h.st.uploads++;  // (+1 per version change seen, whichever path served it)
+        else
+            h.upload(*sp);
+        rst.last_refresh_ms =
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
     }
 
     // how many slots of `words` words each serve `wanted` requests: the power of two >= wanted,
@@ -431,6 +651,10 @@ int list_new(const ketogpu_snapshot *sp, const Opts *opts, H **out, const char *
         h->budget = opts ? opts->state_budget_bytes : 0;
         if (const char *e = getenv(tier_knob)) h->force_tier2 = atoi(e) == 2;
         if (const char *e = getenv(slots_knob)) h->slot_cap = (uint32_t)std::max(atoi(e), 0);
+        if (const char *e = getenv("KETOGPU_LIST_REFRESH")) h->refresh_full = std::string(e) == "full";
+        if (const char *e = getenv("KETOGPU_LIST_ARENA_SLACK")) h->slack_knob = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KETOGPU_LIST_BOUND_STEP"))
+            h->bound_step = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(strtoull(e, nullptr, 10), 1), 1u << 24);
         init(*h);
         h->link = s.link;
         int ndev = 0;
@@ -469,7 +693,7 @@ int list_call(H *h, bool null, size_t n, const char *noun, const uint32_t *limit
         std::lock_guard<std::mutex> lk(h->mu);
         h->t0 = std::chrono::steady_clock::now();
         HIP_CHECK(hipSetDevice(h->device));
-        h->refresh([&](const Snapshot &s) { h->upload(s); });
+        h->refresh(*h);
         f();
     });
 }

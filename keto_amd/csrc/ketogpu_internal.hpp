@@ -193,10 +193,11 @@ struct Snapshot {
     uint64_t version = 0;               // writes applied in place
     uint64_t row_garbage = 0;           // stale group rows left by grown groups (group_col, row_col)
     struct Patch {
-        uint8_t rev;                    // 0: forward row of node, 1: reverse row
+        uint8_t kind;                   // KETOGPU_PATCH_*: 0 the fint row of node, 1 its reverse row,
+                                        // 2 its full forward row (node_row: the subjects handle's rows)
         uint32_t node;
     };
-    std::vector<Patch> patches;         // device rows changed, in write order (engines replay)
+    std::vector<Patch> patches;         // rows changed, in write order (engines and listing handles replay)
     uint64_t patch_base = 0;            // patches trimmed off the front (absolute index of patches[0])
     // engines over this snapshot -> the absolute patch position each has replayed up to;
     // a write trims the log below the smallest
@@ -233,12 +234,12 @@ struct Snapshot {
     mutable std::shared_ptr<const ReachLabels> reach_cache;
     mutable std::shared_future<std::shared_ptr<const ReachLabels>> reach_building;
     mutable uint64_t reach_building_version = ~0ull;
-    // reverse lookup's per-node object types (lookup.hpp type_index_of), derived per version
+    // reverse lookup's per-node object types (lookup.hpp type_index_of): derived once per
+    // snapshot object, since nothing it reads changes in place
     mutable std::shared_ptr<const TypeIndex> type_cache;
-    mutable uint64_t type_cache_version = ~0ull;
-    // subject listing's per-node classes (subjects.hpp class_index_of), derived per version
-    mutable std::shared_ptr<const ClassIndex> class_cache;
-    mutable uint64_t class_cache_version = ~0ull;
+    // subject listing's per-node classes (subjects.hpp class_index_of): derived once and
+    // extended by the ids an in-place write added
+    mutable std::shared_ptr<ClassIndex> class_cache;
     // An engine's way back to its snapshot at teardown: the snapshot's destructor clears it,
     // so an engine freed after its snapshot (a garbage collector's order) skips the
     // deregistration instead of touching freed memory.

@@ -202,7 +202,8 @@ __global__ __launch_bounds__(64) void path_tier1_kernel(Rows g, const uint32_t *
     bool over = false, hit = false;
     uint32_t v = t, pv = kParTarget;
     for (;;) {
-        const uint64_t b = g.off[v], e = g.off[v + 1];
+        uint64_t b, e;
+        row_bounds(g, v, b, e);
         for (uint64_t base = b; base < e && !over && !hit; base += 64) {
             const uint64_t j = base + lane;
             const uint32_t u = j < e ? g.col[j] : kEmpty;
@@ -535,11 +536,24 @@ struct ketogpu_lookup : ListHandle {
     void upload(const Snapshot &s) {
         if (s.has_ambiguous) throw Error(KETOGPU_EINVAL, what + ": the snapshot has shared Subject.String() keys (R4)");
         auto types = type_index_of(s);
-        if (upload_rows(s, s.rev_off.data(), s.rev_off.size(), s.rev_col.data(), s.rev_col.size(),
-                        types->node_type.data(), types->node_type.size(), s.Nx))
-            path_slots = 0, path_slot_max = 0;
+        if (upload_rows(s, s.rev_off.data(), nullptr, s.rev_off.size(), s.rev_col.data(), s.rev_col.size(), 0,
+                        types->node_type.data(), types->node_type.size(), 0, s.Nx))
+            moved();
         st.uploads++;
     }
+
+    // ---- what ListHandle::try_patch asks of a handle.  The reverse rows are uploaded as the
+    // snapshot lays them out, free slots included, and rev_off never moves between rebuilds: a
+    // changed row (KETOGPU_PATCH_REVERSE) is overwritten where it lies.  The types cover the
+    // ids below Nx, which gain no members in place, and the bound is Nx: only g.N follows a
+    // new subject (its reserved reverse row is in the upload already).
+    static constexpr uint8_t kPatchKind = KETOGPU_PATCH_REVERSE;
+    void host_row(const Snapshot &s, uint32_t v, const uint32_t *&p, uint64_t &len, uint64_t &at) const {
+        at = s.rev_off[v], len = s.rev_off[v + 1] - at, p = s.rev_col.data() + at;
+    }
+    const uint32_t *host_keys(const Snapshot &) const { return nullptr; }
+    uint32_t bound_of(const Snapshot &s) const { return s.Nx; }
+    void moved() { path_slots = 0, path_slot_max = 0; }
 
     uint64_t slot_words() const { return ((uint64_t)g.Nx + 31) / 32 + std::max<uint32_t>(g.Ni, 1); }
 
@@ -768,6 +782,10 @@ void ketogpu_lookup_free(ketogpu_lookup *l) { delete l; }
 
 int ketogpu_lookup_stats_get(const ketogpu_lookup *l, ketogpu_lookup_stats *out) {
     return list_stats_get(l, &ketogpu_lookup::st, out);
+}
+
+int ketogpu_lookup_refresh_stats_get(const ketogpu_lookup *l, ketogpu_list_refresh_stats *out) {
+    return list_stats_get<ListHandle>(l, &ListHandle::rst, out);
 }
 
 int ketogpu_lookup_ids(ketogpu_lookup *l, const uint32_t *targets, size_t n, uint32_t type, uint32_t *out,

@@ -22,8 +22,22 @@ struct TypeIndex {
     std::map<std::tuple<int32_t, uint32_t, bool>, uint32_t> ids;
 };
 
-// the index of the snapshot's current version (caller holds the snapshot's shared lock)
+// the index of the snapshot (caller holds the snapshot's shared lock): built once and kept for
+// every version of the same snapshot object (see lookup_host.cpp for why that is sound)
 std::shared_ptr<const TypeIndex> type_index_of(const Snapshot &s);
+
+// the type key of one subject-set node: what type_index_of and class_index_of look up
+struct TypeKeys {
+    std::map<int32_t, bool> empty_ns;  // namespace id -> its configured name is ""
+    explicit TypeKeys(const Snapshot &s) {
+        for (const Namespace &n : s.namespaces) empty_ns[n.id] = n.name.empty();
+    }
+    std::tuple<int32_t, uint32_t, bool> of(const Snapshot &s, uint32_t v) const {
+        auto e = empty_ns.find(s.node_ns[v]);
+        const bool wild = s.node_a[v] == 0 || s.node_b[v] == 0 || (e != empty_ns.end() && e->second);
+        return std::make_tuple(s.node_ns[v], s.node_b[v], wild);
+    }
+};
 
 inline bool type_matches(uint32_t node_type, uint32_t want) {
     return want == KETOGPU_TYPE_ANY ? node_type != KETOGPU_TYPE_NONE : (want != KETOGPU_TYPE_NONE && node_type == want);

@@ -15,23 +15,26 @@
 namespace ketogpu {
 
 std::shared_ptr<const TypeIndex> type_index_of(const Snapshot &s) {
+    // The index reads Nx, the placeholders, and kind, namespace id, object and relation of the
+    // nodes below Nx, and the configured namespaces.  An in-place write changes none of them:
+    // Nx, Ni and the placeholders are fixed between rebuilds (a write that would move a node's
+    // class is refused with KETOGPU_WRITE_CLASS), new subjects take ids in [N, n_cap), which lie
+    // above Nx, the name fields of an existing node are never rewritten, and a new
+    // namespace configuration is a new snapshot object.  So the index built for one version is
+    // the index of every later version of the same object.
     std::lock_guard<std::mutex> lk(s.derived_mu);
-    if (s.type_cache && s.type_cache_version == s.version) return s.type_cache;
+    if (s.type_cache) return s.type_cache;
     auto t = std::make_shared<TypeIndex>();
     t->node_type.assign(s.Nx, KETOGPU_TYPE_NONE);
-    std::map<int32_t, bool> empty_ns;  // namespace id -> its configured name is ""
-    for (const Namespace &n : s.namespaces) empty_ns[n.id] = n.name.empty();
+    const TypeKeys keys(s);
     for (uint32_t v = 0; v < s.Nx; v++) {
         if (v == s.Df || v == s.Dbi || v == s.Dbo || s.node_kind[v] != KETOGPU_SUBJECT_SET) continue;
-        auto e = empty_ns.find(s.node_ns[v]);
-        const bool wild = s.node_a[v] == 0 || s.node_b[v] == 0 || (e != empty_ns.end() && e->second);
-        auto key = std::make_tuple(s.node_ns[v], s.node_b[v], wild);
+        const auto key = keys.of(s, v);
         auto it = t->ids.find(key);
         if (it == t->ids.end()) it = t->ids.emplace(key, (uint32_t)t->ids.size()).first;
         t->node_type[v] = it->second;
     }
     s.type_cache = t;
-    s.type_cache_version = s.version;
     return t;
 }
 

@@ -14,6 +14,10 @@
 //   device each touched forward row fint(g) and reverse row rev(s) is rewritten inside its
 //          own capacity (rows were laid out with free slots, make_writable below) and
 //          logged; engines replay the log at their next call (device_engine.hip: sync).
+//   log    next to those, every rewritten full forward row (node_row) is logged for the
+//          subjects handle, which keeps rows of its own; the listing handles replay the log
+//          like engines (hip_host.hpp: try_patch), and ketogpu_patch_reader_* reads it on the
+//          host (below).
 // Edge records carry the row position and capacity of the node they point at, and
 // capacities never change between rebuilds, so no record outside a touched row changes.
 #include <algorithm>
@@ -21,6 +25,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <new>
 
 #include "ketogpu_internal.hpp"
 
@@ -544,6 +549,9 @@ struct Writer {
             rr.first_bad = -1;
             g.valid = g.full_len = (uint32_t)rows.size();
             S.node_row[v] = rr;
+            // the full forward row of v changed: what a subjects handle replays (not a device
+            // row of the check engine, so not counted in device_rows)
+            S.patches.push_back({KETOGPU_PATCH_FORWARD_FULL, v});
         }
         // Edge records carry the real entry counts of the rows they point at (the free slots
         // are never read through a record): rows holding a record for a node whose count
@@ -628,6 +636,100 @@ uint64_t ketogpu_snapshot_version(const ketogpu_snapshot *sp) {
     const Snapshot &S = *reinterpret_cast<const Snapshot *>(sp);
     std::shared_lock<std::shared_mutex> rd(S.mu);
     return S.version;
+}
+
+}  // extern "C"
+
+// A host-side reader of the patch log: registered like an engine (its position holds the log)
+// and advanced by what it has copied out.
+struct ketogpu_patch_reader {
+    std::shared_ptr<Snapshot::ReaderLink> link;  // cleared when the snapshot is freed first
+    uint64_t pos = 0;
+
+    const Snapshot *snapshot() const {
+        std::lock_guard<std::mutex> lk(link->mu);
+        return link->snap;
+    }
+};
+
+extern "C" {
+
+int ketogpu_patch_reader_new(const ketogpu_snapshot *sp, ketogpu_patch_reader **out) {
+    if (!sp || !out) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *out = nullptr;
+    const Snapshot &S = *reinterpret_cast<const Snapshot *>(sp);
+    auto r = new (std::nothrow) ketogpu_patch_reader();
+    if (!r) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+    std::shared_lock<std::shared_mutex> rd(S.mu);
+    r->link = S.link;
+    r->pos = S.patch_end();
+    S.reader_at(r, r->pos);
+    {
+        std::lock_guard<std::mutex> lk(S.link->mu);
+        S.link->snap = &S;  // the way back to the snapshot; its destructor clears it
+    }
+    *out = r;
+    return KETOGPU_OK;
+}
+
+int ketogpu_patch_reader_next(ketogpu_patch_reader *r, uint8_t *kinds, uint32_t *nodes, size_t capacity, size_t *n) {
+    if (!r || !n || (capacity && (!kinds || !nodes))) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    *n = 0;
+    const Snapshot *sp = r->snapshot();
+    if (!sp) {
+        set_last_error("patch reader: the snapshot was freed");
+        return KETOGPU_EINVAL;
+    }
+    std::shared_lock<std::shared_mutex> rd(sp->mu);
+    if (r->pos < sp->patch_base) {  // (a registered reader is never trimmed past)
+        set_last_error("patch reader: the log was trimmed below the reader");
+        return KETOGPU_EINVAL;
+    }
+    const size_t k = (size_t)std::min<uint64_t>(capacity, sp->patch_end() - r->pos);
+    for (size_t i = 0; i < k; i++) {
+        const Snapshot::Patch &pt = sp->patches[r->pos - sp->patch_base + i];
+        kinds[i] = pt.kind, nodes[i] = pt.node;
+    }
+    r->pos += k;
+    sp->reader_at(r, r->pos);
+    *n = k;
+    return KETOGPU_OK;
+}
+
+int ketogpu_patch_reader_position(const ketogpu_patch_reader *r, uint64_t *position, uint64_t *log_begin,
+                                  uint64_t *log_end) {
+    if (!r) {
+        set_last_error("null argument");
+        return KETOGPU_EINVAL;
+    }
+    const Snapshot *sp = r->snapshot();
+    if (!sp) {
+        set_last_error("patch reader: the snapshot was freed");
+        return KETOGPU_EINVAL;
+    }
+    std::shared_lock<std::shared_mutex> rd(sp->mu);
+    if (position) *position = r->pos;
+    if (log_begin) *log_begin = sp->patch_base;
+    if (log_end) *log_end = sp->patch_end();
+    return KETOGPU_OK;
+}
+
+void ketogpu_patch_reader_free(ketogpu_patch_reader *r) {
+    if (!r) return;
+    {
+        std::lock_guard<std::mutex> lk(r->link->mu);
+        if (r->link->snap) r->link->snap->reader_gone(r);
+    }
+    delete r;
 }
 
 }  // extern "C"

@@ -2,9 +2,11 @@
 //
 // subjects(r, C) lists F(r), the nodes reached from r in >= 1 edge over the rows the check
 // engine sees, restricted to the class C: the least set that holds row(r) and row(x) for every
-// interior x in it (DESIGN.md "Subject listing").  The rows live in HBM as a compact CSR over
-// the expandable nodes (fwd_off / fwd_col), built at upload from the snapshot's host rows; they
-// are neither sorted nor deduplicated, the sets dedup.  The closure, its two tiers and the list
+// interior x in it (DESIGN.md "Subject listing").  The rows live in HBM as a CSR over the
+// expandable nodes (fwd_off / fwd_col), built at upload from the snapshot's host rows: compact
+// on a snapshot that cannot change in place, an arena of rows with room to grow on a writable
+// one, which in-place writes are patched into (DESIGN.md "Listing handles and writes").  The
+// rows are neither sorted nor deduplicated, the sets dedup.  The closure, its two tiers and the list
 // finishes are closure.hpp's, over these rows with the member bound num_nodes; the host side of
 // the handle is hip_host.hpp's ListHandle.  What is here: the class filter, the classification
 // of a root, the seen list and the finish by it, the kernels as bodies over the shared pieces,
@@ -50,8 +52,8 @@ namespace {
 
 constexpr uint32_t kListCapDefault = 65536;  // tier 2: 256 KiB of seen list per slot
 
-// The graph g of every kernel: fwd_off (Nx + 1 offsets), fwd_col, the class of each of the N
-// nodes as the filter key, and the bound N.
+// The graph g of every kernel: fwd_off (Nx + 1 offsets), fwd_col, the rows' ends where they lie
+// in an arena (Rows::end), the class of each of the N nodes as the filter key, and the bound N.
 
 struct SOut {
     ListOut l;
@@ -525,7 +527,7 @@ __global__ __launch_bounds__(kT2Block) void subjects_via_page_tier2_kernel(
 
 struct ketogpu_subjects : ListHandle {
     uint32_t list_cap = kListCapDefault;  // tier 2: a seen list of list_cap per slot (d_aux)
-    std::vector<uint64_t> h_off;          // upload staging
+    std::vector<uint64_t> h_off, h_end;   // upload staging
     std::vector<uint32_t> h_col;
     ketogpu_subjects_stats st{};
     ketogpu_combine_stats cst{};
@@ -535,25 +537,58 @@ struct ketogpu_subjects : ListHandle {
     ketogpu_subjects() : ListHandle("subject listing") {}
 
     // the rows and classes of the snapshot's current version (caller holds its shared lock):
-    // the first `len` entries of every expandable node's row, packed back to back
+    // the first `len` entries of every expandable node's row.  Packed back to back on a
+    // snapshot that cannot change in place (and under KETOGPU_LIST_REFRESH=full).  On a writable
+    // one every row gets the host's growth rule, room for len + len / 4 + 4 entries, in an
+    // arena with `slack` free words behind the last row: a written row is patched where it
+    // lies, or moved to the tail once it has outgrown its room (ListHandle::try_patch).  The
+    // class array has room for the reserved ids.
     void upload(const Snapshot &s) {
         if (s.has_ambiguous) throw Error(KETOGPU_EINVAL, what + ": the snapshot has shared Subject.String() keys (R4)");
         auto classes = class_index_of(s);
+        arena = s.writable && !refresh_full;
         h_off.assign((size_t)s.Nx + 1, 0);
-        for (uint32_t v = 0; v < s.Nx; v++) h_off[v + 1] = h_off[v] + s.node_row[v].len;
-        h_col.resize(h_off[s.Nx]);
+        if (arena) {
+            m_begin.resize(s.Nx), m_cap.resize(s.Nx), h_end.resize(s.Nx);
+            for (uint32_t v = 0; v < s.Nx; v++) {
+                const uint64_t len = s.node_row[v].len, cap = std::min<uint64_t>(len + len / 4 + 4, 0xffffffffu);
+                m_begin[v] = h_off[v], m_cap[v] = (uint32_t)cap;
+                h_end[v] = h_off[v] + len, h_off[v + 1] = h_off[v] + cap;
+            }
+        } else {
+            for (uint32_t v = 0; v < s.Nx; v++) h_off[v + 1] = h_off[v] + s.node_row[v].len;
+        }
+        const uint64_t used = h_off[s.Nx];
+        const uint64_t slack =
+            !arena ? 0 : slack_knob != ~0ull ? slack_knob : std::max<uint64_t>(s.stats.num_edges / 8, 1u << 16);
+        h_col.resize(used);
         for (uint32_t v = 0; v < s.Nx; v++)
             if (s.node_row[v].len) memcpy(h_col.data() + h_off[v], s.row_ptr(v), (size_t)s.node_row[v].len * 4);
-        upload_rows(s, h_off.data(), h_off.size(), h_col.data(), h_col.size(), classes->node_class.data(),
-                    classes->node_class.size(), s.N);
-        std::vector<uint32_t>().swap(h_col);  // (the larger staging array is not kept between uploads)
+        upload_rows(s, h_off.data(), arena ? h_end.data() : nullptr, h_off.size(), h_col.data(), h_col.size(),
+                    used + slack, classes->node_class.data(), s.N, arena ? std::max(s.N, s.n_cap) : s.N, bound_of(s));
+        arena_tail = used, arena_garbage = 0;
+        std::vector<uint32_t>().swap(h_col);  // (the larger staging arrays are not kept between uploads)
+        std::vector<uint64_t>().swap(h_end);
         st.uploads++;
     }
+
+    // ---- what ListHandle::try_patch asks of a handle: the full forward rows the log names
+    // (KETOGPU_PATCH_FORWARD_FULL) go into the arena; new subjects bring a class each and
+    // raise the bound N
+    static constexpr uint8_t kPatchKind = KETOGPU_PATCH_FORWARD_FULL;
+    void host_row(const Snapshot &s, uint32_t v, const uint32_t *&p, uint64_t &len, uint64_t &at) const {
+        at = 0, len = s.node_row[v].len, p = s.row_ptr(v);
+    }
+    const uint32_t *host_keys(const Snapshot &s) const { return class_index_of(s)->node_class.data(); }
+    // the bitmaps span the bound; the kernels take the member bound itself, g.N, which the span
+    // is never below.  With the arena the span is rounded up (ListHandle::bound_step)
+    uint32_t bound_of(const Snapshot &s) const { return arena ? bound_above(s.N) : s.N; }
+    void moved() {}
 
     uint64_t seen_words() const { return std::max<uint32_t>(list_cap, 1); }
 
     uint64_t slot_words() const {
-        return std::max<uint64_t>(((uint64_t)g.N + 31) / 32, 1) + std::max<uint32_t>(g.Ni, 1) + seen_words();
+        return std::max<uint64_t>(bm_words, 1) + std::max<uint32_t>(g.Ni, 1) + seen_words();
     }
 
     uint32_t alloc_slots(uint32_t wanted) { return ListHandle::need_slots(wanted, slot_words(), seen_words()); }
@@ -778,6 +813,10 @@ void ketogpu_subjects_free(ketogpu_subjects *h) { delete h; }
 
 int ketogpu_subjects_stats_get(const ketogpu_subjects *h, ketogpu_subjects_stats *out) {
     return list_stats_get(h, &ketogpu_subjects::st, out);
+}
+
+int ketogpu_subjects_refresh_stats_get(const ketogpu_subjects *h, ketogpu_list_refresh_stats *out) {
+    return list_stats_get<ListHandle>(h, &ListHandle::rst, out);
 }
 
 int ketogpu_subjects_ids(ketogpu_subjects *h, const uint32_t *roots, size_t n, uint32_t cls, uint32_t *out,

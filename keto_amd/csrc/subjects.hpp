@@ -11,12 +11,16 @@ namespace ketogpu {
 // (placeholders stay KETOGPU_TYPE_NONE); from Nx on KETOGPU_CLASS_SUBJECT_ID for a subject id,
 // and for a subject set the type id of its (namespace id, relation, wild) key if an expandable
 // node defines it, else KETOGPU_CLASS_UNTYPED_SET.  N grows under in-place writes (reserved
-// ids), so the array is derived per snapshot version like the type index.
+// ids): the array is built once and extended by the new ids (subjects_host.cpp).
 struct ClassIndex {
     std::vector<uint32_t> node_class;  // N entries
 };
 
-// the index of the snapshot's current version (caller holds the snapshot's shared lock)
+// the class of one node from Nx on: what the full build and the extension both store
+uint32_t class_of(const Snapshot &s, const TypeIndex &types, const TypeKeys &keys, uint32_t v);
+
+// the index of the snapshot's current version (caller holds the snapshot's shared lock); read
+// ids below the snapshot's N only, and only while that lock is held
 std::shared_ptr<const ClassIndex> class_index_of(const Snapshot &s);
 
 // ANY: every class but NONE; NONE and UNTYPED_SET as filters match nothing

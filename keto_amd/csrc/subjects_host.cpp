@@ -15,25 +15,31 @@ namespace ketogpu {
 std::shared_ptr<const ClassIndex> class_index_of(const Snapshot &s) {
     auto types = type_index_of(s);  // (takes derived_mu itself)
     std::lock_guard<std::mutex> lk(s.derived_mu);
-    if (s.class_cache && s.class_cache_version == s.version) return s.class_cache;
-    auto c = std::make_shared<ClassIndex>();
-    c->node_class.assign(s.N, KETOGPU_TYPE_NONE);
-    std::copy(types->node_type.begin(), types->node_type.end(), c->node_class.begin());
-    std::map<int32_t, bool> empty_ns;  // namespace id -> its configured name is ""
-    for (const Namespace &n : s.namespaces) empty_ns[n.id] = n.name.empty();
-    for (uint32_t v = s.Nx; v < s.N; v++) {
-        if (s.node_kind[v] != KETOGPU_SUBJECT_SET) {
-            c->node_class[v] = KETOGPU_CLASS_SUBJECT_ID;
-            continue;
-        }
-        auto e = empty_ns.find(s.node_ns[v]);
-        const bool wild = s.node_a[v] == 0 || s.node_b[v] == 0 || (e != empty_ns.end() && e->second);
-        auto it = types->ids.find(std::make_tuple(s.node_ns[v], s.node_b[v], wild));
-        c->node_class[v] = it != types->ids.end() ? it->second : KETOGPU_CLASS_UNTYPED_SET;
+    // The classes below Nx are the types, which never change in place (type_index_of), and the
+    // class of a node from Nx on follows from its own name fields and the type ids, which do
+    // not change either: an in-place write only appends the ids [old N, N).  The cached array
+    // is therefore extended by those, at a cost of O(new nodes).  Its storage is reserved up to
+    // n_cap, so the extension copies nothing; it happens under derived_mu in the first call of
+    // a version, while every holder of an earlier pointer reads ids below the N it saw, under
+    // a snapshot lock that excludes writes.
+    if (!s.class_cache) {
+        auto c = std::make_shared<ClassIndex>();
+        c->node_class.reserve(std::max(s.N, s.n_cap));
+        c->node_class.assign(types->node_type.begin(), types->node_type.end());
+        s.class_cache = c;
     }
-    s.class_cache = c;
-    s.class_cache_version = s.version;
-    return c;
+    std::vector<uint32_t> &cls = s.class_cache->node_class;
+    if (cls.size() < s.N) {
+        const TypeKeys keys(s);
+        for (uint32_t v = (uint32_t)cls.size(); v < s.N; v++) cls.push_back(class_of(s, *types, keys, v));
+    }
+    return s.class_cache;
+}
+
+uint32_t class_of(const Snapshot &s, const TypeIndex &types, const TypeKeys &keys, uint32_t v) {
+    if (s.node_kind[v] != KETOGPU_SUBJECT_SET) return KETOGPU_CLASS_SUBJECT_ID;
+    auto it = types.ids.find(keys.of(s, v));
+    return it != types.ids.end() ? it->second : KETOGPU_CLASS_UNTYPED_SET;
 }
 
 }  // namespace ketogpu

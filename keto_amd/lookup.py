@@ -808,8 +808,9 @@ def _all_lists(raw, n, cap, sort, invalid):
 
 class _Handle:
     """a listing handle of the library over a snapshot: ketogpu_<ABI>_new / _free / _stats_get
-    with the structs OPTS and STATS.  A write to a writable snapshot is seen by the next call
-    (the rows are uploaded again when the snapshot's version has moved)."""
+    with the structs OPTS and STATS.  A write to a writable snapshot is seen by the next call:
+    the handle replays the snapshot's patch log and rewrites the rows the write touched on the
+    GPU (refresh_stats() tells how; KETOGPU_LIST_REFRESH=full uploads everything instead)."""
 
     def __init__(self, snapshot, device=0, state_budget_bytes=0):
         self.L = L.lib()
@@ -841,6 +842,11 @@ class _Handle:
 
     def stats(self):
         return self._stats(self.STATS(), "stats_get")
+
+    def refresh_stats(self):
+        """how the handle followed the snapshot's writes (ketogpu_list_refresh_stats): full
+        uploads, patched refreshes, rows patched and moved, words uploaded, the fallbacks"""
+        return self._stats(L.ListRefreshStats(), "refresh_stats_get")
 
     def _ids_raw(self, call, requests, filters, capacity):
         """one cursor call ketogpu_<ABI>_<call>(handle, *request arrays, n, *filters, ...) ->

@@ -25,6 +25,47 @@ def subject_struct(subject):
     return L.Subject(L.SUBJECT_SET, None, L.b(subject.namespace), L.b(subject.object), L.b(subject.relation))
 
 
+class PatchReader:
+    """The patch log of a writable snapshot from now on: read() returns what writes logged
+    since the last read, in write order, as (kind, node) pairs, kind being L.PATCH_* .  While
+    it is open the snapshot keeps the log from the reader's position on."""
+
+    def __init__(self, snapshot):
+        self.L = L.lib()
+        self.snapshot = snapshot  # (kept alive)
+        h = C.c_void_p()
+        L.check(self.L.ketogpu_patch_reader_new(snapshot.h, C.byref(h)))
+        self.h = h
+
+    def read(self, chunk=4096):
+        out = []
+        kinds, nodes, n = np.empty(chunk, np.uint8), np.empty(chunk, np.uint32), C.c_size_t()
+        while True:
+            L.check(self.L.ketogpu_patch_reader_next(self.h, kinds.ctypes.data, nodes.ctypes.data, chunk, C.byref(n)))
+            out += [(int(k), int(v)) for k, v in zip(kinds[:n.value], nodes[:n.value])]
+            if n.value < chunk:
+                return out
+
+    def position(self):
+        """(the reader's position, the first entry the snapshot still keeps, the log's end)"""
+        pos, lo, hi = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        L.check(self.L.ketogpu_patch_reader_position(self.h, C.byref(pos), C.byref(lo), C.byref(hi)))
+        return pos.value, lo.value, hi.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.ketogpu_patch_reader_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Snapshot:
     """`order` names the backend whose ORDER BY the rows follow (include/ketogpu.h
     KETOGPU_ORDER_*): "sqlite" (default), "mysql-bin", "cockroach" (NULLs first) or
@@ -123,6 +164,10 @@ class Snapshot:
     def version(self):
         """writes applied in place so far"""
         return int(self.L.ketogpu_snapshot_version(self.h))
+
+    def patch_reader(self):
+        """a reader of the rows later in-place writes rewrite (ketogpu_patch_reader_*)"""
+        return PatchReader(self)
 
     def apply(self, insert_rows=(), delete_rows=()):
         """the next version: raw rows (namespace_id, object, relation, subject_id|None, ss_ns,
