@@ -1453,6 +1453,69 @@ int ketogpu_patch_reader_position(const ketogpu_patch_reader *r, uint64_t *posit
                                   uint64_t *log_end);
 void ketogpu_patch_reader_free(ketogpu_patch_reader *r);
 
+/* ------------------------------------------------------------- expand as id arrays
+ * BuildTree in batches.  A tree is two parallel arrays in preorder: nodes[k], a snapshot node
+ * id, and num_children[k]; node k is a Union iff num_children[k] > 0 (a Union of ketogpu_expand
+ * always has children) and a Leaf otherwise.  It is the layout of ketogpu_tree_nodes with ids
+ * in place of strings; ketogpu_tree_from_ids turns it into a ketogpu_tree, so
+ * ketogpu_tree_nodes and ketogpu_tree_json read a device answer.
+ *
+ * ketogpu_snapshot_expand_ids is ketogpu_expand's walk on the host without strings, over a root
+ * that is a snapshot node (KETOGPU_EINVAL for any other id): the same visited map (one per tree,
+ * keyed by Subject.String()), the same paging, KETOGPU_ENOTFOUND exactly where ketogpu_expand
+ * returns it (the arrays are NULL then).  *n == 0 is the nil tree.  *flags bit 0
+ * (KETOGPU_EXPAND_NEEDS_HOST): the walk made a first visit to a node whose query has a row
+ * with an unknown namespace, whether or not the reference then fails (it fails only when it
+ * fetches the page with that row).  rest_depth 0 is the nil tree, KETOGPU_EXPAND_DEPTH_ALL no
+ * limit (KETOGPU_DEPTH_ALL is 0, which is the nil tree here).  Free both arrays with
+ * ketogpu_free.
+ *
+ * ketogpu_subjects_expand is the device call, on the subjects handle, with the output contract
+ * of ketogpu_subjects_ids: count[i] the exact tree size; begin[i] the tree's offset in both
+ * output arrays, or KETOGPU_LOOKUP_TRUNCATED (nothing of the tree was written) or
+ * KETOGPU_LOOKUP_INVALID (roots[i] >= num_nodes and not KETOGPU_NODE_NONE; status NIL);
+ * *needed the sum of the counts; capacity 0 with NULL outputs only counts.  status[i]:
+ * KETOGPU_EXPAND_OK; KETOGPU_EXPAND_NIL (count 0: the nil tree; KETOGPU_NODE_NONE, a subject
+ * set without rows, rest_depth 0); KETOGPU_EXPAND_HOST (count 0, nothing written: ask
+ * ketogpu_expand), given exactly when the host twin would set KETOGPU_EXPAND_NEEDS_HOST, or
+ * when the snapshot has shared Subject.String() keys (R4; every request then).  A subject-id
+ * root gives one leaf.  Roots that are no snapshot node (dynamic wildcard queries, unknown
+ * names) are ketogpu_expand's business.  Every OK tree equals the host twin's word for word.
+ *
+ * Tier 1 is one wave per request: a pre-order walk with the visited set and the DFS stack in
+ * LDS, 64 row entries per step.  A request that opens more than set_capacity nodes moves to
+ * tier 2 (KETOGPU_SUBJECTS_TIER=2 forces it): one workgroup per request, the slot's bitmap as
+ * the visited set, 256 entries per step, and a stack of 2 words per node that has rows in
+ * global memory, counted against state_budget_bytes.  A request walks twice, once to count and
+ * once to write; a count-only call walks once.  Expand calls count only here: no other
+ * statistics move.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+#define KETOGPU_EXPAND_DEPTH_ALL 0xFFFFFFFFu
+#define KETOGPU_EXPAND_NEEDS_HOST 1u
+#define KETOGPU_EXPAND_OK 0u
+#define KETOGPU_EXPAND_NIL 1u
+#define KETOGPU_EXPAND_HOST 2u
+int ketogpu_snapshot_expand_ids(const ketogpu_snapshot *s, uint32_t root, uint32_t rest_depth, uint32_t **nodes,
+                                uint32_t **num_children, uint64_t *n, uint32_t *flags);
+/* KETOGPU_EINVAL for arrays that are no preorder tree of snapshot nodes; n == 0: *tree = NULL */
+int ketogpu_tree_from_ids(const ketogpu_snapshot *s, const uint32_t *nodes, const uint32_t *num_children, uint64_t n,
+                          ketogpu_tree **tree);
+typedef struct {
+    uint64_t requests;       /* since creation: requests passed in                         */
+    uint64_t tier1_requests; /* walked by the one-wave LDS kernel                          */
+    uint64_t tier2_requests; /* walked by the workgroup-per-request kernel                 */
+    uint64_t tier2_rounds;   /* tier-2 launches of expand calls                            */
+    uint64_t host_requests;  /* status KETOGPU_EXPAND_HOST                                 */
+    uint64_t nodes_produced; /* sum of the exact tree sizes                                */
+    uint64_t truncated_trees;
+    uint32_t slots;          /* tier 2: requests per expand round (0 before the first)     */
+    double last_call_ms;     /* host wall time of the last expand call                     */
+} ketogpu_expand_stats;
+int ketogpu_subjects_expand_stats_get(const ketogpu_subjects *h, ketogpu_expand_stats *out);
+int ketogpu_subjects_expand(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *rest_depth, size_t n,
+                            uint32_t *out_nodes, uint32_t *out_children, uint64_t capacity, uint64_t *begin,
+                            uint64_t *count, uint32_t *status, uint64_t *needed);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

@@ -397,6 +397,21 @@ class ListRefreshStats(C.Structure):
 PATCH_FORWARD_INTERIOR, PATCH_REVERSE, PATCH_FORWARD_FULL = 0, 1, 2
 
 
+# include/ketogpu.h expand as id arrays
+EXPAND_DEPTH_ALL = 0xFFFFFFFF
+EXPAND_NEEDS_HOST = 1
+EXPAND_OK, EXPAND_NIL, EXPAND_HOST = 0, 1, 2
+
+
+class ExpandStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "requests", "tier1_requests", "tier2_requests", "tier2_rounds", "host_requests", "nodes_produced",
+        "truncated_trees")] + [("slots", C.c_uint32), ("last_call_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol declared in include/ketogpu.h, with its ctypes signature
 vp, i32, u32, sz = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t
 SIGNATURES = {
@@ -570,6 +585,11 @@ SIGNATURES = {
                                            C.POINTER(C.c_uint64)]),
     "ketogpu_lookup_page_via": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
     "ketogpu_subjects_page_via": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "ketogpu_snapshot_expand_ids": (C.c_int, [vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64),
+                                              C.POINTER(u32)]),
+    "ketogpu_tree_from_ids": (C.c_int, [vp, vp, vp, C.c_uint64, C.POINTER(vp)]),
+    "ketogpu_subjects_expand_stats_get": (C.c_int, [vp, C.POINTER(ExpandStats)]),
+    "ketogpu_subjects_expand": (C.c_int, [vp, vp, vp, sz, vp, vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

@@ -157,9 +157,12 @@ struct ListHandle {
     DBuf<unsigned long long> d_front;  // depth calls: the frontier per request
     DBuf<uint32_t> d_via, d_hops;      // via calls: the arrays parallel to d_out
     DBuf<uint32_t> d_viast;            // ... and tier 2's parent and hop words: 2 x bound per slot
+    DBuf<uint32_t> d_xstack;           // expand calls: tier 2's DFS stack, 2 x Nx words per slot
     uint32_t slots = 0, slot_max = 0;  // tier 2: allocated slots; what budget and knob allow (0: not yet known)
     uint32_t pair_slots = 0, pair_slot_max = 0;  // `slots` for combined calls: a slot has a second bitmap too
     uint32_t via_slots = 0, via_slot_max = 0;    // `slots` for via calls: a slot has parent and hop words too
+    uint32_t expand_slots = 0, expand_slot_max = 0;  // `slots` for expand calls: a slot has a DFS stack too
+    uint64_t expand_stack_words = 0;                 // ... of this many words
     uint32_t bound = 0;                // the member bound the closures take: the bitmaps span it
     uint64_t bm_words = 0;
 
@@ -205,7 +208,7 @@ struct ListHandle {
         d_end.drop(), d_seg.drop(), d_stage.drop(), h_stage.drop(), h_seg.drop();
         d_off.drop(), d_col.drop(), d_label.drop(), d_req.drop(), d_req2.drop(), d_ovf.drop(), d_out.drop();
         d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop(), d_bm.drop(), d_wl.drop();
-        d_aux.drop(), d_bm2.drop(), d_front.drop(), d_via.drop(), d_hops.drop(), d_viast.drop();
+        d_aux.drop(), d_bm2.drop(), d_front.drop(), d_via.drop(), d_hops.drop(), d_viast.drop(), d_xstack.drop();
     }
 
     double ms_of_call() const {
@@ -217,6 +220,7 @@ struct ListHandle {
         slots = 0, slot_max = 0, d_bm.drop(), d_wl.drop(), d_aux.drop();
         pair_slots = 0, pair_slot_max = 0, d_bm2.drop();
         via_slots = 0, via_slot_max = 0, d_viast.drop();
+        expand_slots = 0, expand_slot_max = 0, d_xstack.drop();
     }
 
     // one version's rows and labels to the device, all of them: a full upload.  `end`: the rows'
@@ -262,6 +266,7 @@ struct ListHandle {
     //   host_keys(s)                the filter keys of all N nodes when new nodes have one, else null
     //   bound_of(s)                 the member bound
     //   moved()                     (bound, Ni) moved: the handle's own tier-2 state goes too
+    //   patched(s)                  a patched refresh succeeded: patch_nodes are the rows it rewrote
     template <class H>
     bool try_patch(const Snapshot &s, H &h) {
         if (!s.writable || refresh_full || !registered) return false;
@@ -378,7 +383,7 @@ struct ListHandle {
         if (sp->version == version) return;
         const auto r0 = std::chrono::steady_clock::now();
         if (try_patch(*sp, h))
-            h.st.uploads++;  // (+1 per version change seen, whichever path served it)
+            h.st.uploads++, h.patched(*sp);  // (+1 per version change seen, whichever path served it)
         else
             h.upload(*sp);
         rst.last_refresh_ms =
@@ -446,6 +451,24 @@ struct ListHandle {
         k = std::min<uint64_t>(k, need((uint32_t)k));  // (at least one)
         d_viast.need(k * vw);
         return via_slots = (uint32_t)k;
+    }
+
+    // tier 2's state for an expand call: need(k)'s slots (the handle's own need_slots, `words`
+    // words in all) plus a DFS stack of two words per frame in d_xstack.  A frame is a node that
+    // has a row and each is opened once, so 2 x Nx words per slot hold any walk; they are counted
+    // against the budget with the rest, so an expand round may have fewer slots.  The words are
+    // never cleared: the stack height says which of them hold.
+    template <class Need>
+    uint32_t need_expand_slots(uint32_t wanted, uint64_t words, Need &&need) {
+        const uint64_t sw = 2 * std::max<uint64_t>(g.Nx, 1);
+        if (sw != expand_stack_words) expand_slots = 0, expand_slot_max = 0;
+        uint64_t k = slots_for(wanted, words + sw, expand_slot_max);
+        if (k <= expand_slots && expand_slots <= slots) return expand_slots;
+        expand_slots = 0;
+        k = std::min<uint64_t>(k, need((uint32_t)k));  // (at least one)
+        d_xstack.need(k * sw);
+        expand_stack_words = sw;
+        return expand_slots = (uint32_t)k;
     }
 
     // a via call's device arrays next to d_out, `words` each (null where the caller wants none)

@@ -8,7 +8,9 @@
 //     internal/x/graph/graph_utils.go:13-35); used only for requests the GPU flags as
 //     touching an ambiguous key (R4), where the sequential order decides the answer,
 //   * BuildTree (internal/expand/engine.go:30-98): sequential DFS over the ordered rows;
-//     its output order depends on DB order, so it stays a host walk of the snapshot.
+//     its output order depends on DB order.  Expander is the walk with strings, for any
+//     subject; IdExpander the same walk over a root that is a node, as id arrays, and the
+//     yardstick of the device walk (expand_tree.hpp).
 #include <string>
 #include <unordered_set>
 
@@ -189,6 +191,65 @@ struct Expander {
             return true;
         }
         return build(u, s.key_id[u], s.node_row[u], s.row_ptr(u), depth, out);
+    }
+};
+
+// Expander's walk over a root that is a node, iterative and without strings: the tree as two
+// preorder arrays (include/ketogpu.h "expand as id arrays").  A union's child count is its
+// query's length, known when it is opened, so the arrays are written front to back.
+struct IdExpander {
+    const Snapshot &s;
+    std::unordered_set<uint32_t> visited;  // as Expander's: one map per tree, keyed by Subject.String()
+    uint64_t ps;
+    std::vector<uint32_t> nodes, kids;
+    uint32_t flags = 0;
+
+    enum { NIL, LEAF, UNION };
+
+    // the page that starts at row b is fetched (Expander::build's page loop)
+    void fetch(const RowRef &q, uint64_t b) const {
+        const uint64_t e = std::min<uint64_t>(b + ps, q.full_len);
+        if (q.first_bad >= 0 && (uint64_t)q.first_bad < e)
+            throw Error(KETOGPU_ENOTFOUND, "Unknown namespace id in a tuple of the expanded set");
+    }
+
+    // Expander::build up to its first page, for the subject set u at rest depth >= 1
+    int open(uint32_t u, uint32_t depth) {
+        if (!visited.insert(s.key_id[u]).second) return NIL;
+        const RowRef &q = s.node_row[u];
+        if (q.first_bad >= 0) flags |= KETOGPU_EXPAND_NEEDS_HOST;
+        fetch(q, 0);
+        if (!q.full_len) return NIL;
+        return depth <= 1 ? LEAF : UNION;
+    }
+
+    void emit(uint32_t u, uint32_t k) { nodes.push_back(u), kids.push_back(k); }
+
+    void run(uint32_t root, uint32_t depth) {
+        if (!depth) return;
+        if (s.node_kind[root] != KETOGPU_SUBJECT_SET) return emit(root, 0);
+        struct Frame {
+            uint32_t v, depth;  // depth: the children's rest depth, >= 1
+            uint64_t i;
+        };
+        std::vector<Frame> st;
+        const int r = open(root, depth);
+        if (r == NIL) return;
+        emit(root, r == UNION ? s.node_row[root].full_len : 0);
+        if (r == UNION) st.push_back({root, depth - 1, 0});
+        while (!st.empty()) {
+            Frame &f = st.back();
+            const RowRef &q = s.node_row[f.v];
+            if (f.i == q.full_len) {
+                st.pop_back();
+                continue;
+            }
+            if (f.i && f.i % ps == 0) fetch(q, f.i);
+            const uint32_t u = s.row_ptr(f.v)[f.i++], cd = f.depth;
+            const int c = s.node_kind[u] == KETOGPU_SUBJECT_SET ? open(u, cd) : (int)LEAF;
+            emit(u, c == UNION ? s.node_row[u].full_len : 0);
+            if (c == UNION) st.push_back({u, cd - 1, 0});  // (f is stale from here on)
+        }
     }
 };
 
@@ -421,5 +482,77 @@ int ketogpu_tree_json(const ketogpu_tree *t, char **json) {
 }
 
 void ketogpu_tree_free(ketogpu_tree *t) { delete t; }
+
+int ketogpu_snapshot_expand_ids(const ketogpu_snapshot *sp, uint32_t root, uint32_t rest_depth, uint32_t **nodes,
+                                uint32_t **num_children, uint64_t *n, uint32_t *flags) {
+    if (nodes) *nodes = nullptr;
+    if (num_children) *num_children = nullptr;
+    if (n) *n = 0;
+    if (flags) *flags = 0;
+    try {
+        if (!sp || !nodes || !num_children || !n) throw Error(KETOGPU_EINVAL, "null argument");
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        std::shared_lock<std::shared_mutex> rd(s.mu);  // against in-place writes
+        if (root >= s.N) throw Error(KETOGPU_EINVAL, "expand: the root is not a node of the snapshot");
+        IdExpander ex{s, {}, (uint64_t)std::max(s.page_size, 1), {}, {}};
+        try {
+            ex.run(root, rest_depth);
+        } catch (const Error &) {
+            if (flags) *flags = ex.flags;
+            throw;
+        }
+        if (flags) *flags = ex.flags;
+        const size_t k = ex.nodes.size();
+        if (!k) return KETOGPU_OK;  // nil tree
+        uint32_t *a = (uint32_t *)malloc(k * 4), *b = (uint32_t *)malloc(k * 4);
+        if (!a || !b) {
+            free(a), free(b);
+            throw std::bad_alloc();
+        }
+        memcpy(a, ex.nodes.data(), k * 4), memcpy(b, ex.kids.data(), k * 4);
+        *nodes = a, *num_children = b, *n = k;
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
+
+int ketogpu_tree_from_ids(const ketogpu_snapshot *sp, const uint32_t *nodes, const uint32_t *num_children, uint64_t n,
+                          ketogpu_tree **tree) {
+    try {
+        if (!sp || !tree || (n && (!nodes || !num_children))) throw Error(KETOGPU_EINVAL, "null argument");
+        *tree = nullptr;
+        if (!n) return KETOGPU_OK;
+        const Snapshot &s = *reinterpret_cast<const Snapshot *>(sp);
+        std::shared_lock<std::shared_mutex> rd(s.mu);  // against in-place writes
+        uint64_t open = 1;  // nodes the preorder still owes
+        for (uint64_t k = 0; k < n; k++) {
+            if (nodes[k] >= s.N) throw Error(KETOGPU_EINVAL, "tree: an id outside the snapshot");
+            if (!open) throw Error(KETOGPU_EINVAL, "tree: the arrays hold more than one tree");
+            open += (uint64_t)num_children[k] - 1;
+        }
+        if (open) throw Error(KETOGPU_EINVAL, "tree: the arrays end inside the tree");
+        auto t = std::make_unique<ketogpu_tree>();
+        t->nodes.resize(n);
+        for (uint64_t k = 0; k < n; k++) {
+            ketogpu_tree_node &o = t->nodes[k];
+            o.type = num_children[k] ? KETOGPU_NODE_UNION : KETOGPU_NODE_LEAF;
+            o.num_children = num_children[k];
+            fill_subject(s, *t, nodes[k], o.subject);
+        }
+        *tree = t.release();
+        return KETOGPU_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return KETOGPU_ENOMEM;
+    }
+}
 
 }  // extern "C"

@@ -554,6 +554,7 @@ struct ketogpu_lookup : ListHandle {
     const uint32_t *host_keys(const Snapshot &) const { return nullptr; }
     uint32_t bound_of(const Snapshot &s) const { return s.Nx; }
     void moved() { path_slots = 0, path_slot_max = 0; }
+    void patched(const Snapshot &) {}
 
     uint64_t slot_words() const { return ((uint64_t)g.Nx + 31) / 32 + std::max<uint32_t>(g.Ni, 1); }
 

@@ -35,12 +35,18 @@
 // member, the node whose row granted it and its hop count: via.hpp's bodies, which keep a parent
 // and a level per first visit.
 //
+// The expand call (ketogpu_subjects_expand) is no listing: it writes BuildTree's tree of each
+// root as two preorder arrays, word for word what the host walk gives.  The bodies are
+// expand_tree.hpp's: an ordered depth-first walk over the same rows, with the sets, slots and
+// reservations of the closures.
+//
 // Every index is validated before it is used: roots against N, and against Nx before fwd_off
 // is touched; row entries against N before the class array or a bitmap is.
 #include <hip/hip_runtime.h>
 
 #include "combine.hpp"
 #include "depth.hpp"
+#include "expand_tree.hpp"
 #include "hip_host.hpp"
 #include "subjects.hpp"
 #include "via.hpp"
@@ -523,6 +529,34 @@ __global__ __launch_bounds__(kT2Block) void subjects_via_page_tier2_kernel(
         s, [&](uint32_t u) { return class_ok(g, u, cls); }, [&](uint32_t u) { return any_class(g, u); });
 }
 
+// ---------------------------------------------------------------------- expand
+// ketogpu_subjects_expand: the bodies are expand_tree.hpp's.  Tier 2 uses the slot's bitmap and
+// seen list and adds a DFS stack of stack_words words per slot.
+__global__ __launch_bounds__(64) void subjects_expand_tier1_kernel(expand::Graph x, const uint32_t *roots,
+                                                                   const uint32_t *depths, uint32_t n,
+                                                                   int force_tier2, expand::TreeOut o,
+                                                                   uint32_t *ovf_list, unsigned int *ovf_count) {
+    __shared__ expand::T1Lds s;
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    expand::tier1_tree(x, roots, depths, i, lane, force_tier2, o, ovf_list, ovf_count, s);
+}
+
+__global__ __launch_bounds__(kT2Block) void subjects_expand_tier2_kernel(expand::Graph x, const uint32_t *roots,
+                                                                         const uint32_t *depths, expand::TreeOut o,
+                                                                         const uint32_t *ovf_list, uint32_t first,
+                                                                         uint32_t *bitmaps, uint64_t bm_words,
+                                                                         uint32_t *seen_lists, uint32_t list_cap,
+                                                                         uint32_t *stacks, uint64_t stack_words) {
+    __shared__ expand::T2Lds s;
+    __shared__ unsigned long long s_base;
+    const uint32_t i = ovf_list[first + blockIdx.x];
+    const expand::Slot sl{bitmaps + (uint64_t)blockIdx.x * bm_words, bm_words,
+                          seen_lists + (uint64_t)blockIdx.x * list_cap, list_cap,
+                          stacks + (uint64_t)blockIdx.x * stack_words};
+    expand::tier2_tree(x, roots[i], depths[i], i, sl, s, &s_base, o);
+}
+
 }  // namespace
 
 struct ketogpu_subjects : ListHandle {
@@ -533,8 +567,52 @@ struct ketogpu_subjects : ListHandle {
     ketogpu_combine_stats cst{};
     ketogpu_depth_stats dst{};
     ketogpu_via_stats vst{};
+    ketogpu_expand_stats xst{};
+    // expand calls: a bit per node whose query has a row with an unknown namespace
+    // (node_row[v].first_bad >= 0).  It spans all N nodes, since a node whose rows are all bad
+    // has no row here and still fails on the host.  The host keeps a mirror; the device array is
+    // used only while some bit is set, so a snapshot without bad rows pays nothing
+    std::vector<uint32_t> h_bad;
+    DBuf<uint32_t> d_bad;
+    bool has_bad = false;
+    uint32_t bad_n = 0;  // the nodes the mirror covers
 
     ketogpu_subjects() : ListHandle("subject listing") {}
+    ~ketogpu_subjects() { d_bad.drop(); }
+
+    void push_bad() {
+        has_bad = std::any_of(h_bad.begin(), h_bad.end(), [](uint32_t w) { return w != 0; });
+        if (!has_bad) return;
+        d_bad.need(h_bad.size());
+        HIP_CHECK(hipMemcpyAsync(d_bad.p, h_bad.data(), h_bad.size() * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+
+    // v's bit from the snapshot's current rows -> it changed
+    bool put_bad(const Snapshot &s, uint32_t v) {
+        const uint32_t bit = 1u << (v & 31), want = s.node_row[v].first_bad >= 0 ? bit : 0;
+        const bool changed = (h_bad[v >> 5] & bit) != want;
+        h_bad[v >> 5] = (h_bad[v >> 5] & ~bit) | want;
+        return changed;
+    }
+
+    void upload_bad(const Snapshot &s) {
+        h_bad.assign(((size_t)std::max(s.N, s.n_cap) + 31) / 32 + 1, 0);
+        for (uint32_t v = 0; v < s.N; v++) put_bad(s, v);
+        bad_n = s.N;
+        push_bad();
+    }
+
+    // what a patched refresh asks of the handle: the bits of the rows it rewrote and of new nodes
+    void patched(const Snapshot &s) {
+        bool changed = h_bad.size() < ((size_t)s.N + 31) / 32 + 1;  // (the device array must span N too)
+        if (changed) h_bad.resize(((size_t)s.N + 31) / 32 + 1, 0);
+        for (uint32_t v : patch_nodes)
+            if (v < s.N) changed |= put_bad(s, v);
+        for (uint32_t v = bad_n; v < s.N; v++) changed |= put_bad(s, v);
+        bad_n = s.N;
+        if (changed) push_bad();
+    }
 
     // the rows and classes of the snapshot's current version (caller holds its shared lock):
     // the first `len` entries of every expandable node's row.  Packed back to back on a
@@ -569,6 +647,7 @@ struct ketogpu_subjects : ListHandle {
         arena_tail = used, arena_garbage = 0;
         std::vector<uint32_t>().swap(h_col);  // (the larger staging arrays are not kept between uploads)
         std::vector<uint64_t>().swap(h_end);
+        upload_bad(s);
         st.uploads++;
     }
 
@@ -777,6 +856,82 @@ struct ketogpu_subjects : ListHandle {
         count_via_finishes(t, frontier, n);
     }
 
+    // tier 2's state for an expand call (ListHandle::need_expand_slots): the handle's slots as
+    // they are, seen lists included
+    uint32_t need_expand_state(uint32_t wanted) {
+        return xst.slots = need_expand_slots(wanted, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+    }
+
+    // is the snapshot one with shared Subject.String() keys now?  (in-place writes can make it one)
+    bool snapshot_ambiguous() {
+        const Snapshot *sp;
+        {
+            std::lock_guard<std::mutex> lk(link->mu);
+            sp = link->snap;
+        }
+        if (!sp) throw Error(KETOGPU_EINVAL, what + ": the snapshot was freed");
+        std::shared_lock<std::shared_mutex> rd(sp->mu);
+        return sp->has_ambiguous;
+    }
+
+    // ... then the visited map is not keyed by node: every request is the host's
+    void expand_all_host(size_t n, uint64_t *begin, uint64_t *count, uint32_t *status, uint64_t *needed) {
+        *needed = 0;
+        for (size_t i = 0; i < n; i++) begin[i] = 0, count[i] = 0, status[i] = KETOGPU_EXPAND_HOST;
+        xst.requests += n, xst.host_requests += n;
+        xst.last_call_ms = ms_of_call();
+    }
+
+    // ketogpu_subjects_expand: run()'s output contract with two output arrays and a status
+    void run_expand(const uint32_t *roots, const uint32_t *depths, size_t n, uint32_t *out_nodes,
+                    uint32_t *out_children, uint64_t capacity, uint64_t *begin, uint64_t *count, uint32_t *status,
+                    uint64_t *needed) {
+        Tally t{};
+        *needed = 0;
+        xst.requests += n;
+        if (!n) return;
+        d_req.need(n), d_req2.need(n), d_ovf.need(n), d_begin.need(n), d_count.need(n), d_ret.need(n);
+        d_ctr.need(kCtrs), d_out.need(capacity), d_via.need(capacity);
+        HIP_CHECK(hipMemcpyAsync(d_req.p, roots, n * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(d_req2.p, depths, n * 4, hipMemcpyHostToDevice, stream));
+        const expand::Graph x{g, has_bad ? d_bad.p : nullptr};
+        const expand::TreeOut o{list_out(capacity), d_via.p, d_ret.p};
+        run_tiers(
+            xst, t,
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_expand_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, x, d_req.p, d_req2.p,
+                        (uint32_t)n, force_tier2 ? 1 : 0, o, d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return need_expand_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(subjects_expand_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, x, d_req.p, d_req2.p, o,
+                        d_ovf.p, first, d_bm.p, bm_words, d_aux.p, list_cap, d_xstack.p, expand_stack_words);
+            },
+            [&](Tally &t) { read_ctrs(t); });  // (the cursor has moved)
+        HIP_CHECK(hipMemcpyAsync(begin, d_begin.p, n * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(count, d_count.p, n * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(status, d_ret.p, n * 4, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        // (the written trees tile a prefix of both arrays: no word outside a written tree is touched)
+        const uint64_t written = std::min<uint64_t>(written_end(begin, count, n), capacity);
+        if (written && out_nodes) {
+            HIP_CHECK(hipMemcpyAsync(out_nodes, d_out.p, written * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(out_children, d_via.p, written * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        *needed = t.ctr[0];
+        uint64_t unlisted = 0;
+        for (size_t i = 0; i < n; i++) {
+            unlisted += begin[i] == KETOGPU_LOOKUP_INVALID || roots[i] == NONE;
+            xst.host_requests += status[i] == KETOGPU_EXPAND_HOST;
+        }
+        xst.tier2_requests += t.ovf;
+        xst.tier1_requests += n - t.ovf - unlisted;
+        xst.nodes_produced += t.ctr[0];
+        xst.truncated_trees += t.ctr[1];
+        xst.last_call_ms = ms_of_call();
+    }
+
     void count_via_finishes(const Tally &t, uint64_t *frontier, size_t n) {
         vst.list_finishes += t.ctr[3];
         vst.scan_finishes += t.ctr[4];
@@ -891,6 +1046,27 @@ int ketogpu_subjects_page_via(ketogpu_subjects *h, const uint32_t *roots, const 
                               uint64_t *frontier) {
     return list_call(h, n && (!roots || !out || !returned || !count || !remaining), n, "roots", &limit, [&] {
         h->run_page_via(roots, max_depth, from, n, cls, limit, out, via, hops, returned, count, remaining, frontier);
+    });
+}
+
+int ketogpu_subjects_expand_stats_get(const ketogpu_subjects *h, ketogpu_expand_stats *out) {
+    return list_stats_get(h, &ketogpu_subjects::xst, out);
+}
+
+int ketogpu_subjects_expand(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *rest_depth, size_t n,
+                            uint32_t *out_nodes, uint32_t *out_children, uint64_t capacity, uint64_t *begin,
+                            uint64_t *count, uint32_t *status, uint64_t *needed) {
+    if (!h || !needed || (n && (!roots || !rest_depth || !begin || !count || !status)) ||
+        (capacity && (!out_nodes || !out_children)))
+        return einval("null argument");
+    if (n >= (1ull << 31)) return einval(h->what + ": more than 2^31 - 1 roots in one call");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->t0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipSetDevice(h->device));
+        if (h->snapshot_ambiguous()) return h->expand_all_host(n, begin, count, status, needed);
+        h->refresh(*h);
+        h->run_expand(roots, rest_depth, n, out_nodes, out_children, capacity, begin, count, status, needed);
     });
 }
 

@@ -7,6 +7,7 @@ caller gets the reference's responses from the new engines:
     GET  /check    internal/check/handler.go:85-107   200 {"allowed":true} | 403 {"allowed":false} | 400
     POST /check    internal/check/handler.go:128-146  same; a JSON decode error is 400
     GET  /expand   internal/expand/handler.go:78-92   200 tree | null, 400 bad max-depth, 404 unknown namespace
+    POST /expand/batch   (no Keto counterpart) a list of {subject, max-depth} -> per item what GET /expand answers
     POST /check/batch  (new, SURVEY.md 8(f) row 2)    200 {"results": [{"allowed": bool} | {"error": ...}]}
     GET  /list/objects   (new, DESIGN.md "Sorted, paged lists")  200 {"objects": [...], "next_page_token", "total"}
     GET  /list/subjects  (new, same section)                     200 {"subjects": [...], "next_page_token", "total"}
@@ -174,9 +175,11 @@ class Handler:
     lookup.Subjects on the device, lookup.HostLookup / lookup.HostSubjects without one); without
     them the list routes answer 404.  `lookup` also serves /check/explain through its Explain."""
 
-    def __init__(self, check_engine: check.Engine, expand_engine: expand.Engine, lookup=None, subjects=None):
+    def __init__(self, check_engine: check.Engine, expand_engine: expand.Engine, lookup=None, subjects=None,
+                 expand_batch=None):
         self.check = check_engine
         self.expand = expand_engine
+        self.expand_batch = expand_batch  # an expand.DeviceEngine (None: /expand/batch walks on the host)
         self.lookup = lookup
         self.subjects = subjects
 
@@ -223,6 +226,51 @@ class Handler:
         except expand.NotFound as e:
             return self._error(404, str(e))
         return 200, (tree.to_node() if tree else None)
+
+    def post_expand_batch(self, body):
+        """[{"subject_set": {...} | "subject_id": "...", "max-depth": n}, ...] -> a list with,
+        per item, what GET /expand answers: the tree, null, or the error body (404 unknown
+        namespace, 400 bad max-depth or subject).  max-depth is a JSON integer or a string as
+        the query parameter takes it.  One batch of the expand engine serves the trees: on the
+        device where self.expand_batch is an expand.DeviceEngine, else the host's id walk."""
+        try:
+            items = json.loads(body)
+            if isinstance(items, dict):
+                items = items["items"]
+            if not isinstance(items, list):
+                raise BadRequest("expected a list of {subject, max-depth}")
+        except (ValueError, KeyError, TypeError, BadRequest) as e:
+            return self._error(400, f"Unable to decode JSON payload: {e}")
+        results = [None] * len(items)
+        subjects, depths, where = [], [], []
+        for i, it in enumerate(items):
+            try:
+                if not isinstance(it, dict):
+                    raise BadRequest("expected an object")
+                raw = it.get("max-depth")
+                try:
+                    depth = raw if isinstance(raw, int) and not isinstance(raw, bool) else go_parse_int(raw)
+                except ValueError as e:
+                    raise BadRequest(f"strconv.ParseInt: parsing {json.dumps(raw if isinstance(raw, str) else '')}: {e}")
+                d = it.get("subject") if isinstance(it.get("subject"), dict) else it
+                if d.get("subject_id") is not None and d.get("subject_set") is not None:
+                    raise BadRequest("exactly one of subject_set or subject_id has to be provided")
+                if d.get("subject_id") is not None:
+                    subject = SubjectID(_json_string(d, "subject_id"))
+                else:
+                    ss = d.get("subject_set", d)
+                    if not isinstance(ss, dict):
+                        raise BadRequest(f"json: cannot unmarshal {type(ss).__name__} into field subject_set of type object")
+                    subject = SubjectSet(*(_json_string(ss, k) if ss.get(k) is not None else ""
+                                           for k in ("namespace", "object", "relation")))
+            except BadRequest as e:
+                results[i] = self._error(400, str(e))[1]
+                continue
+            subjects.append(subject), depths.append(max(-1, min(depth, 2**31 - 1))), where.append(i)
+        engine = self.expand_batch if self.expand_batch is not None else self.expand
+        for i, t in zip(where, engine.build_trees_batch(subjects, depths)):
+            results[i] = self._error(404, str(t))[1] if isinstance(t, expand.NotFound) else (t.to_node() if t else None)
+        return 200, results
 
     def post_check_batch(self, body):
         """{"tuples": [...]} -> {"results": [...]}, one engine call for the whole batch"""
@@ -473,6 +521,8 @@ def serve(handler: Handler, port: int):  # pragma: no cover - demo harness
                 self._send(*handler.post_check(body))
             elif path == "/check/batch":
                 self._send(*handler.post_check_batch(body))
+            elif path == "/expand/batch":
+                self._send(*handler.post_expand_batch(body))
             else:
                 self._send(404, {"error": {"code": 404, "status": "Not Found"}})
 
@@ -497,7 +547,8 @@ def main():  # pragma: no cover - demo harness
     except _lib.KetoError as e:  # shared Subject.String() keys (R4): the list routes answer 404
         print(f"no list routes: {e}")
         lists = (None, None)
-    serve(Handler(check.Engine(snap), expand.Engine(snap), *lists), a.port)
+    device = expand.DeviceEngine(snap, subjects=lists[1]) if lists[1] is not None else None
+    serve(Handler(check.Engine(snap), expand.Engine(snap), *lists, expand_batch=device), a.port)
 
 
 if __name__ == "__main__":
