@@ -1516,6 +1516,44 @@ int ketogpu_subjects_expand(ketogpu_subjects *h, const uint32_t *roots, const ui
                             uint32_t *out_nodes, uint32_t *out_children, uint64_t capacity, uint64_t *begin,
                             uint64_t *count, uint32_t *status, uint64_t *needed);
 
+/* ------------------------------------------------------- chip-wide closures */
+/* ketogpu_subjects_ids / ketogpu_lookup_ids with a third way to run a closure, the wide tier, in
+ * place of tier 2 (DESIGN.md "Chip-wide closures").  The output contract is that of the plain
+ * calls word for word: count[i] exact; a list written completely or KETOGPU_LOOKUP_TRUNCATED; an
+ * id outside the snapshot KETOGPU_LOOKUP_INVALID; KETOGPU_NODE_NONE and ids without rows the
+ * empty list; *needed the sum of the counts; capacity 0 with out NULL counts only; ids and lists
+ * in any order, without duplicates; the same filters, the same refusal of a snapshot with shared
+ * Subject.String() keys, the same following of in-place writes.
+ *
+ * Tier 1 runs as in the plain calls.  A request whose closure passes set_capacity runs in the
+ * wide tier, `slots` requests per round: level-synchronous across the whole device, one launch
+ * per level, its work items chunks of `chunk` entries of one row, so that a row of a million
+ * entries is read by about 500 waves; the host reads the number of new items behind each level.
+ * KETOGPU_SUBJECTS_TIER=2 / KETOGPU_LOOKUP_TIER=2 send every request that has a row to the wide
+ * tier, KETOGPU_SUBJECTS_SLOTS / KETOGPU_LOOKUP_SLOTS cap its round.  The round's queue of work
+ * items is counted against state_budget_bytes with tier 2's state, whose bitmaps it shares.
+ * Wide calls count only here: no other statistics move, and no plain call is routed here.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+typedef struct {
+    uint64_t requests;       /* since creation: requests passed to wide calls              */
+    uint64_t tier1_requests; /* answered by the one-wave LDS kernel                        */
+    uint64_t wide_requests;  /* answered by the wide tier                                  */
+    uint64_t wide_rounds;    /* rounds of the wide tier (each serves up to `slots`)        */
+    uint64_t levels;         /* level launches, summed over the rounds                     */
+    uint64_t items;          /* work items processed                                       */
+    uint64_t ids_produced;   /* sum of the exact list sizes                                */
+    uint64_t truncated_lists;
+    uint32_t slots;          /* requests per wide round (0 before the first round)         */
+    uint32_t chunk;          /* row entries per work item                                  */
+    double last_call_ms;     /* host wall time of the last wide call                       */
+} ketogpu_wide_stats;
+int ketogpu_subjects_wide_stats_get(const ketogpu_subjects *h, ketogpu_wide_stats *out);
+int ketogpu_lookup_wide_stats_get(const ketogpu_lookup *l, ketogpu_wide_stats *out);
+int ketogpu_subjects_ids_wide(ketogpu_subjects *h, const uint32_t *roots, size_t n, uint32_t cls, uint32_t *out,
+                              uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
+int ketogpu_lookup_ids_wide(ketogpu_lookup *l, const uint32_t *targets, size_t n, uint32_t type, uint32_t *out,
+                            uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

@@ -412,6 +412,16 @@ class ExpandStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# include/ketogpu.h chip-wide closures
+class WideStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "requests", "tier1_requests", "wide_requests", "wide_rounds", "levels", "items", "ids_produced",
+        "truncated_lists")] + [("slots", C.c_uint32), ("chunk", C.c_uint32), ("last_call_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol declared in include/ketogpu.h, with its ctypes signature
 vp, i32, u32, sz = C.c_void_p, C.c_int32, C.c_uint32, C.c_size_t
 SIGNATURES = {
@@ -590,6 +600,10 @@ SIGNATURES = {
     "ketogpu_tree_from_ids": (C.c_int, [vp, vp, vp, C.c_uint64, C.POINTER(vp)]),
     "ketogpu_subjects_expand_stats_get": (C.c_int, [vp, C.POINTER(ExpandStats)]),
     "ketogpu_subjects_expand": (C.c_int, [vp, vp, vp, sz, vp, vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_subjects_wide_stats_get": (C.c_int, [vp, C.POINTER(WideStats)]),
+    "ketogpu_lookup_wide_stats_get": (C.c_int, [vp, C.POINTER(WideStats)]),
+    "ketogpu_subjects_ids_wide": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_ids_wide": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

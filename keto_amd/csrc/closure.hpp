@@ -17,6 +17,8 @@
 //           worklist of Ni entries in global memory; tier2_closure's level loop with
 //           __syncthreads() runs the closure to its end whatever its size.  scan_count / scan_write
 //           write the list from the bitmap and clear it; page_count_clear is the paged call's scan.
+//   (wide.hpp holds a third way to run a closure, spread over the whole device, over tier 2's
+//   bitmaps and with the same reservation.)
 //
 // Both list finishes end the same way (reserve): count the members, reserve exactly that many
 // ids of `out` with one device-scope atomicAdd on a cursor, and write the list with plain

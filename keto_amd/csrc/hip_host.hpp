@@ -3,7 +3,8 @@
 // ListHandle: the state both handles carry, the drivers of their calls (tier 1, the read of the
 // overflow count, tier 2 in rounds of `slots`, the copies back) and the shared parts of their
 // ABI entry points, and how a handle follows in-place writes: the patched refresh (try_patch,
-// list_patch_kernel) with the full upload as its fallback.  A handle adds its graph struct, its
+// list_patch_kernel) with the full upload as its fallback, and the wide tier's state and round
+// (wide.hpp: need_wide_slots, wide_round, run_wide).  A handle adds its graph struct, its
 // upload, what the patched refresh asks of it, its launches (passed to the drivers as callables)
 // and its statistics.
 #pragma once
@@ -25,6 +26,7 @@
 #include "ketogpu_internal.hpp"
 #include "paged_finish.hpp"
 #include "via.hpp"
+#include "wide.hpp"
 
 namespace ketogpu {
 
@@ -163,6 +165,14 @@ struct ListHandle {
     uint32_t via_slots = 0, via_slot_max = 0;    // `slots` for via calls: a slot has parent and hop words too
     uint32_t expand_slots = 0, expand_slot_max = 0;  // `slots` for expand calls: a slot has a DFS stack too
     uint64_t expand_stack_words = 0;                 // ... of this many words
+    // the wide tier (wide.hpp): the round's queue of work items and its counters; the bitmaps
+    // are tier 2's.  The queue's size follows (Ni, col_words)
+    DBuf<wide::Item> d_wq;
+    DBuf<unsigned long long> d_wctr;
+    PBuf<unsigned long long> h_wtail;  // the tail and the error word, as read behind each level
+    uint32_t wide_slots = 0, wide_slot_max = 0;
+    uint64_t wide_col_words = 0, wide_qcap = 0;
+    ketogpu_wide_stats wst{};
     uint32_t bound = 0;                // the member bound the closures take: the bitmaps span it
     uint64_t bm_words = 0;
 
@@ -209,6 +219,7 @@ struct ListHandle {
         d_off.drop(), d_col.drop(), d_label.drop(), d_req.drop(), d_req2.drop(), d_ovf.drop(), d_out.drop();
         d_begin.drop(), d_count.drop(), d_ctr.drop(), d_from.drop(), d_ret.drop(), d_bm.drop(), d_wl.drop();
         d_aux.drop(), d_bm2.drop(), d_front.drop(), d_via.drop(), d_hops.drop(), d_viast.drop(), d_xstack.drop();
+        d_wq.drop(), d_wctr.drop(), h_wtail.drop();
     }
 
     double ms_of_call() const {
@@ -221,6 +232,7 @@ struct ListHandle {
         pair_slots = 0, pair_slot_max = 0, d_bm2.drop();
         via_slots = 0, via_slot_max = 0, d_viast.drop();
         expand_slots = 0, expand_slot_max = 0, d_xstack.drop();
+        wide_slots = 0, wide_slot_max = 0, d_wq.drop(), d_wctr.drop();
     }
 
     // one version's rows and labels to the device, all of them: a full upload.  `end`: the rows'
@@ -471,6 +483,78 @@ struct ListHandle {
         return expand_slots = (uint32_t)k;
     }
 
+    // the wide tier's state: need(k)'s slots (the handle's own need_slots, `words` words in all:
+    // the wide tier uses their bitmaps) plus the round's queue, wide::queue_items items of three
+    // words, and its counters; all of it counted against the budget, so a wide round may have
+    // fewer slots.  The queue is allocated again when col_words moved (an upload with more
+    // edges); drop_tier2 drops it when (bound, Ni) move.  Neither is ever cleared: the tail says
+    // which items hold, and a round zeroes its counters itself.
+    template <class Need>
+    uint32_t need_wide_slots(uint32_t wanted, uint64_t words, Need &&need) {
+        if (col_words != wide_col_words) wide_slots = 0, wide_slot_max = 0;
+        const uint64_t per = 3 * wide::queue_items(1, g.Ni, col_words) + 2 * wide::kPerSlot;
+        uint64_t k = slots_for(wanted, words + per, wide_slot_max);
+        if (k <= wide_slots && wide_slots <= slots) return wide_slots;
+        wide_slots = 0;
+        k = std::min<uint64_t>(k, need((uint32_t)k));  // (at least one)
+        wide_qcap = wide::queue_items(k, g.Ni, col_words);
+        d_wq.need(wide_qcap), d_wctr.need(wide::ctr_words(k)), h_wtail.need(wide::kHead);
+        wide_col_words = col_words;
+        return wide_slots = (uint32_t)k;
+    }
+
+    // the queue's tail behind what is enqueued so far: the wide tier's one host wait per level
+    unsigned long long wide_tail() {
+        HIP_CHECK(hipMemcpyAsync(h_wtail.p, d_wctr.p, wide::kHead * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        return h_wtail.p[wide::kTail];
+    }
+
+    // One round of the wide tier: the requests d_ovf[first .. first + k) with slots 0 .. k - 1.
+    // rows: the ids below it have a row.  level(w, lb, le) launches the handle's level kernel
+    // over the items [lb, le), write(w) its write kernel; seed and reservation are wide.hpp's own.
+    // A queue that proved too small fails the call before anything is written, bitmaps zeroed.
+    template <class Level, class Write>
+    void wide_round(uint32_t first, uint32_t k, uint32_t rows, uint64_t capacity, Level &&level, Write &&write) {
+        const wide::State w{d_bm.p, bm_words, d_wq.p, wide_qcap, d_wctr.p, k, rows};
+        HIP_CHECK(hipMemsetAsync(d_wctr.p, 0, wide::ctr_words(k) * 8, stream));
+        KLAUNCH(wide::seed_kernel, dim3(k), dim3(64), 0, stream, g, d_req.p, d_ovf.p, first, w);
+        unsigned long long lb = 0, le = wide_tail();
+        while (lb < le && !h_wtail.p[wide::kError]) {
+            level(w, lb, le);
+            wst.levels++, wst.items += le - lb;
+            lb = le, le = wide_tail();
+        }
+        if (h_wtail.p[wide::kError]) {
+            HIP_CHECK(hipMemsetAsync(d_bm.p, 0, (uint64_t)k * std::max<uint64_t>(bm_words, 1) * 4, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            throw Error(KETOGPU_EDEVICE, what + ": the wide tier's queue is too small for this round");
+        }
+        KLAUNCH(wide::reserve_kernel, dim3((k + 63) / 64), dim3(64), 0, stream, d_ovf.p, first, w, list_out(capacity));
+        write(w);
+    }
+
+    // the write kernel's grid: a workgroup per tile of one slot's bitmap
+    dim3 wide_write_grid(uint32_t k) const {
+        return dim3((unsigned)std::max<uint64_t>((bm_words + wide::kTile - 1) / wide::kTile, 1), k);
+    }
+
+    // a wide call, counted in wst: run_cursor with rounds of the wide tier in tier 2's place.
+    // need(overflows) -> the slots of a round, round(first, k) one round
+    template <class Unlisted, class T1, class Need, class Round>
+    void run_wide(const uint32_t *req, size_t n, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                  uint64_t *needed, Unlisted &&unlisted, T1 &&tier1, Need &&need, Round &&round) {
+        struct {  // (what run_cursor counts, under tier 2's names)
+            uint64_t requests = 0, tier1_requests = 0, tier2_requests = 0, tier2_rounds = 0, ids_produced = 0,
+                     truncated_lists = 0;
+        } c;
+        run_cursor(c, req, n, out, capacity, begin, count, needed, unlisted, tier1, need, round);
+        wst.requests += c.requests, wst.tier1_requests += c.tier1_requests, wst.wide_requests += c.tier2_requests;
+        wst.wide_rounds += c.tier2_rounds, wst.ids_produced += c.ids_produced;
+        wst.truncated_lists += c.truncated_lists;
+        wst.last_call_ms = ms_of_call();
+    }
+
     // a via call's device arrays next to d_out, `words` each (null where the caller wants none)
     via::ViaOut via_out(const uint32_t *via, const uint32_t *hops, uint64_t words) {
         if (via) d_via.need(words);
@@ -679,6 +763,7 @@ int list_new(const ketogpu_snapshot *sp, const Opts *opts, H **out, const char *
         if (const char *e = getenv("KETOGPU_LIST_BOUND_STEP"))
             h->bound_step = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(strtoull(e, nullptr, 10), 1), 1u << 24);
         init(*h);
+        h->wst.chunk = wide::kChunk;
         h->link = s.link;
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || h->device < 0 || h->device >= ndev)

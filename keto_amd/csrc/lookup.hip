@@ -29,6 +29,9 @@
 // member, the node whose row granted it and its hop count: via.hpp's bodies, which keep a parent
 // and a level per first visit.
 //
+// The wide call (ketogpu_lookup_ids_wide) is the full-list call with tier 1's overflows run by
+// wide.hpp's level-synchronous tier, spread over the whole device, instead of tier 2.
+//
 // Every index is validated before it is used: targets against num_nodes before rev_off is
 // touched, row entries against num_expandable before the type array or a bitmap is.
 #include <hip/hip_runtime.h>
@@ -520,6 +523,22 @@ __global__ __launch_bounds__(kT2Block) void lookup_via_page_tier2_kernel(
         [&](uint32_t u) { return any_type(g, u); });
 }
 
+// ---------------------------------------------------------------------- the wide tier
+// ketogpu_lookup_ids_wide: the bodies are wide.hpp's, over the reverse rows: the ids below N
+// have a row, the member bound is Nx.  The slot's bitmap is tier 2's; worklists are not used.
+__global__ __launch_bounds__(wide::kBlock) void lookup_wide_level_kernel(Rows g, uint32_t type, wide::State w,
+                                                                         unsigned long long lb,
+                                                                         unsigned long long le) {
+    wide::level(g, g.Nx, w, lb, le, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
+__global__ __launch_bounds__(wide::kBlock) void lookup_wide_write_kernel(Rows g, uint32_t type, wide::State w,
+                                                                         ListOut o) {
+    __shared__ unsigned int s_cnt;
+    __shared__ unsigned long long s_at;
+    wide::write(w, o, &s_cnt, &s_at, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
 }  // namespace
 
 struct ketogpu_lookup : ListHandle {
@@ -594,6 +613,33 @@ struct ketogpu_lookup : ListHandle {
                         d_ovf.p, first, d_bm.p, bm_words, d_wl.p);
             });
         st.last_call_ms = ms_of_call();
+    }
+
+    // ketogpu_lookup_ids_wide: run() with tier 1's overflows in rounds of the wide tier
+    void run_ids_wide(const uint32_t *targets, size_t n, uint32_t type, uint32_t *out, uint64_t capacity,
+                      uint64_t *begin, uint64_t *count, uint64_t *needed) {
+        ListHandle::run_wide(
+            targets, n, out, capacity, begin, count, needed,
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || targets[i] == NONE; },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, (uint32_t)n, type,
+                        force_tier2 ? 1 : 0, list_out(capacity), d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) {
+                return wst.slots = need_wide_slots(ovf, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+            },
+            [&](uint32_t first, uint32_t k) {
+                wide_round(
+                    first, k, g.N, capacity,
+                    [&](const wide::State &w, unsigned long long lb, unsigned long long le) {
+                        KLAUNCH(lookup_wide_level_kernel, dim3(wide::level_grid(le - lb)), dim3(wide::kBlock), 0,
+                                stream, g, type, w, lb, le);
+                    },
+                    [&](const wide::State &w) {
+                        KLAUNCH(lookup_wide_write_kernel, wide_write_grid(k), dim3(wide::kBlock), 0, stream, g, type,
+                                w, list_out(capacity));
+                    });
+            });
     }
 
     // the paged call: run() with the ordered finish
@@ -793,6 +839,16 @@ int ketogpu_lookup_ids(ketogpu_lookup *l, const uint32_t *targets, size_t n, uin
                        uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
     return list_call(l, !needed || (n && (!targets || !begin || !count)) || (capacity && !out), n, "targets", nullptr,
                      [&] { l->run(targets, n, type, out, capacity, begin, count, needed); });
+}
+
+int ketogpu_lookup_wide_stats_get(const ketogpu_lookup *l, ketogpu_wide_stats *out) {
+    return list_stats_get<ListHandle>(l, &ListHandle::wst, out);
+}
+
+int ketogpu_lookup_ids_wide(ketogpu_lookup *l, const uint32_t *targets, size_t n, uint32_t type, uint32_t *out,
+                            uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
+    return list_call(l, !needed || (n && (!targets || !begin || !count)) || (capacity && !out), n, "targets", nullptr,
+                     [&] { l->run_ids_wide(targets, n, type, out, capacity, begin, count, needed); });
 }
 
 int ketogpu_lookup_page(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *from, size_t n, uint32_t type,

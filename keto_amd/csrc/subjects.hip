@@ -40,6 +40,9 @@
 // expand_tree.hpp's: an ordered depth-first walk over the same rows, with the sets, slots and
 // reservations of the closures.
 //
+// The wide call (ketogpu_subjects_ids_wide) is the full-list call with tier 1's overflows run by
+// wide.hpp's level-synchronous tier, spread over the whole device, instead of tier 2.
+//
 // Every index is validated before it is used: roots against N, and against Nx before fwd_off
 // is touched; row entries against N before the class array or a bitmap is.
 #include <hip/hip_runtime.h>
@@ -557,6 +560,23 @@ __global__ __launch_bounds__(kT2Block) void subjects_expand_tier2_kernel(expand:
     expand::tier2_tree(x, roots[i], depths[i], i, sl, s, &s_base, o);
 }
 
+// ---------------------------------------------------------------------- the wide tier
+// ketogpu_subjects_ids_wide: the bodies are wide.hpp's, over the forward rows: the ids below Nx
+// have a row, the member bound is N.  The slot's bitmap is tier 2's; seen lists and worklists
+// are not used.
+__global__ __launch_bounds__(wide::kBlock) void subjects_wide_level_kernel(Rows g, uint32_t cls, wide::State w,
+                                                                           unsigned long long lb,
+                                                                           unsigned long long le) {
+    wide::level(g, g.N, w, lb, le, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
+__global__ __launch_bounds__(wide::kBlock) void subjects_wide_write_kernel(Rows g, uint32_t cls, wide::State w,
+                                                                           ListOut o) {
+    __shared__ unsigned int s_cnt;
+    __shared__ unsigned long long s_at;
+    wide::write(w, o, &s_cnt, &s_at, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
 }  // namespace
 
 struct ketogpu_subjects : ListHandle {
@@ -696,6 +716,33 @@ struct ketogpu_subjects : ListHandle {
                 KLAUNCH(subjects_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, g, d_req.p, cls,
                         subjects_out(capacity), d_ovf.p, first, d_bm.p, bm_words, d_wl.p, d_aux.p, list_cap);
             }));
+    }
+
+    // ketogpu_subjects_ids_wide: run() with tier 1's overflows in rounds of the wide tier
+    void run_ids_wide(const uint32_t *roots, size_t n, uint32_t cls, uint32_t *out, uint64_t capacity,
+                      uint64_t *begin, uint64_t *count, uint64_t *needed) {
+        ListHandle::run_wide(
+            roots, n, out, capacity, begin, count, needed,
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || roots[i] == NONE; },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, (uint32_t)n, cls,
+                        force_tier2 ? 1 : 0, subjects_out(capacity), d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) {
+                return wst.slots = need_wide_slots(ovf, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+            },
+            [&](uint32_t first, uint32_t k) {
+                wide_round(
+                    first, k, g.Nx, capacity,
+                    [&](const wide::State &w, unsigned long long lb, unsigned long long le) {
+                        KLAUNCH(subjects_wide_level_kernel, dim3(wide::level_grid(le - lb)), dim3(wide::kBlock), 0,
+                                stream, g, cls, w, lb, le);
+                    },
+                    [&](const wide::State &w) {
+                        KLAUNCH(subjects_wide_write_kernel, wide_write_grid(k), dim3(wide::kBlock), 0, stream, g, cls,
+                                w, list_out(capacity));
+                    });
+            });
     }
 
     // the paged call: run() with the ordered finish
@@ -978,6 +1025,16 @@ int ketogpu_subjects_ids(ketogpu_subjects *h, const uint32_t *roots, size_t n, u
                          uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
     return list_call(h, !needed || (n && (!roots || !begin || !count)) || (capacity && !out), n, "roots", nullptr,
                      [&] { h->run(roots, n, cls, out, capacity, begin, count, needed); });
+}
+
+int ketogpu_subjects_wide_stats_get(const ketogpu_subjects *h, ketogpu_wide_stats *out) {
+    return list_stats_get<ListHandle>(h, &ListHandle::wst, out);
+}
+
+int ketogpu_subjects_ids_wide(ketogpu_subjects *h, const uint32_t *roots, size_t n, uint32_t cls, uint32_t *out,
+                              uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
+    return list_call(h, !needed || (n && (!roots || !begin || !count)) || (capacity && !out), n, "roots", nullptr,
+                     [&] { h->run_ids_wide(roots, n, cls, out, capacity, begin, count, needed); });
 }
 
 int ketogpu_subjects_page(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *from, size_t n, uint32_t cls,

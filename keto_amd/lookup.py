@@ -34,6 +34,10 @@ group (ketogpu_*_ids_depth / ketogpu_*_page_depth, DESIGN.md "Depth-limited list
 request (DEPTH_ALL: no limit) and also return `frontier`, the interior members at exactly that
 distance; `list_*_depth_batch` return names and `complete`, and the named calls take a keyword
 `max_depth`.  `host_lookup_depth` / `host_subjects_depth` are the level-by-level CPU twins.
+
+The full-list calls take a keyword `wide` (ketogpu_*_ids_wide, DESIGN.md "Chip-wide closures"): the
+same lists, with the closures too large for one wave spread over the whole device instead of one
+workgroup each; `wide_stats()` counts them.  The CPU twins accept and ignore it.
 """
 import ctypes as C
 
@@ -967,7 +971,83 @@ class _Handle:
         return out[:n], returned[:n], count[:n], remaining[:n]
 
 
-class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth, _ObjectsVia):
+def _no_wide_with(wide, max_depth, with_via):
+    """wide=True lists whole closures (ketogpu_*_ids_wide): there is no wide depth or via call"""
+    if wide and (max_depth is not None or with_via):
+        raise ValueError("wide=True takes neither max_depth nor with_via")
+
+
+class _ObjectLists:
+    """the full object lists over self.lookup_ids_raw and self.snapshot.  wide: the device
+    handle runs large closures in the wide tier (DESIGN.md "Chip-wide closures"); the CPU twin
+    accepts and ignores it"""
+
+    def lookup_ids(self, targets, type_id=TYPE_ANY, capacity=None, wide=False):
+        """-> one ascending uint32 array per target.  The first call uses `capacity` ids
+        (default 64 per target); only the targets whose lists were truncated are issued
+        again, with capacity = what they need.  An id outside the snapshot raises EINVAL."""
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        return _all_lists(lambda idx, cap: self.lookup_ids_raw(targets[idx], type_id, cap, wide=wide), len(targets),
+                          64 * len(targets) if capacity is None else int(capacity), True,
+                          lambda k: f"target {int(targets[k])} is outside the snapshot")
+
+    def _objects(self, ids):
+        return sorted(self.snapshot.node_info(int(v))["id"] for v in ids)
+
+    def list_objects_batch(self, namespace, relation, subjects, max_depth=None, with_via=False, wide=False):
+        """per subject: the sorted object names o with Check(namespace:o#relation@subject); with
+        max_depth, those within that many hops (list_objects_depth_batch's lists); with_via:
+        (name, via, hops) instead of names (list_objects_via_batch)"""
+        _no_wide_with(wide, max_depth, with_via)
+        if with_via:
+            return self.list_objects_via_batch(namespace, relation, subjects, max_depth)
+        if max_depth is not None:
+            return self.list_objects_depth_batch(namespace, relation, subjects, max_depth)[0]
+        ty = self.snapshot.type_id(namespace, relation)
+        targets = resolve_subjects(self.snapshot, list(subjects))
+        if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
+            return [[] for _ in targets]
+        return [self._objects(ids) for ids in self.lookup_ids(targets, ty, wide=wide)]
+
+    def ListObjects(self, namespace, relation, subject, max_depth=None, with_via=False, wide=False):
+        return self.list_objects_batch(namespace, relation, [subject], max_depth, with_via, wide)[0]
+
+
+class _SubjectLists:
+    """the full subject lists over self.subject_ids_raw and self.snapshot; wide as in _ObjectLists"""
+
+    def subject_ids(self, roots, cls=TYPE_ANY, capacity=None, wide=False):
+        """-> one ascending uint32 array per root.  The first call uses `capacity` ids (default
+        64 per root); only the roots whose lists were truncated are issued again, with
+        capacity = what they need.  An id outside the snapshot raises EINVAL."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        return _all_lists(lambda idx, cap: self.subject_ids_raw(roots[idx], cls, cap, wide=wide), len(roots),
+                          64 * len(roots) if capacity is None else int(capacity), True,
+                          lambda k: f"root {int(roots[k])} is outside the snapshot")
+
+    def list_subjects_batch(self, roots, kind="ids", max_depth=None, with_via=False, wide=False):
+        """per (namespace, object, relation) root: the subjects s with Check(root@s), SubjectIDs
+        then SubjectSets, each sorted.  kind: "ids" (subject ids only), "any", or a
+        (namespace, relation) pair (subject sets of that type; an unknown pair lists nothing).
+        With max_depth: those within that many hops (list_subjects_depth_batch's lists); with_via:
+        (subject, via, hops) instead of subjects (list_subjects_via_batch)"""
+        _no_wide_with(wide, max_depth, with_via)
+        if with_via:
+            return self.list_subjects_via_batch(roots, kind, max_depth)
+        if max_depth is not None:
+            return self.list_subjects_depth_batch(roots, max_depth, kind)[0]
+        roots = list(roots)
+        cls = _class_of_kind(self.snapshot, kind)
+        ids = resolve_roots(self.snapshot, roots)
+        if cls == TYPE_NONE:
+            return [[] for _ in roots]
+        return [_subjects_of(self.snapshot, v) for v in self.subject_ids(ids, cls, wide=wide)]
+
+    def ListSubjects(self, namespace, object, relation, kind="ids", max_depth=None, with_via=False, wide=False):
+        return self.list_subjects_batch([(namespace, object, relation)], kind, max_depth, with_via, wide)[0]
+
+
+class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth, _ObjectsVia, _ObjectLists):
     """device handle over a snapshot's reverse rows"""
     ABI, OPTS, STATS = "lookup", L.LookupOpts, L.LookupStats
 
@@ -987,18 +1067,13 @@ class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth, _Ob
         """one ketogpu_lookup_page_depth call (_page_depth_raw)"""
         return self._page_depth_raw(targets, max_depth, from_ids, type_id, limit)
 
-    def lookup_ids_raw(self, targets, type_id=TYPE_ANY, capacity=0):
-        """one ketogpu_lookup_ids call (_ids_raw)"""
-        return self._ids_raw("ids", [targets], [int(type_id)], capacity)
+    def lookup_ids_raw(self, targets, type_id=TYPE_ANY, capacity=0, wide=False):
+        """one ketogpu_lookup_ids call (_ids_raw); wide: one ketogpu_lookup_ids_wide call, the
+        same results with the large closures spread over the whole device"""
+        return self._ids_raw("ids_wide" if wide else "ids", [targets], [int(type_id)], capacity)
 
-    def lookup_ids(self, targets, type_id=TYPE_ANY, capacity=None):
-        """-> one ascending uint32 array per target.  The first call uses `capacity` ids
-        (default 64 per target); only the targets whose lists were truncated are issued
-        again, with capacity = what they need.  An id outside the snapshot raises EINVAL."""
-        targets = np.ascontiguousarray(targets, dtype=np.uint32)
-        return _all_lists(lambda idx, cap: self.lookup_ids_raw(targets[idx], type_id, cap), len(targets),
-                          64 * len(targets) if capacity is None else int(capacity), True,
-                          lambda k: f"target {int(targets[k])} is outside the snapshot")
+    def wide_stats(self):
+        return self._stats(L.WideStats(), "wide_stats_get")
 
     def path_stats(self):
         return self._stats(L.LookupPathStats(), "path_stats_get")
@@ -1015,27 +1090,6 @@ class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth, _Ob
         """one ketogpu_lookup_page call (_page_raw)"""
         return self._page_raw(targets, from_ids, type_id, limit)
 
-    # ---- names
-    def _objects(self, ids):
-        return sorted(self.snapshot.node_info(int(v))["id"] for v in ids)
-
-    def list_objects_batch(self, namespace, relation, subjects, max_depth=None, with_via=False):
-        """per subject: the sorted object names o with Check(namespace:o#relation@subject); with
-        max_depth, those within that many hops (list_objects_depth_batch's lists); with_via:
-        (name, via, hops) instead of names (list_objects_via_batch)"""
-        if with_via:
-            return self.list_objects_via_batch(namespace, relation, subjects, max_depth)
-        if max_depth is not None:
-            return self.list_objects_depth_batch(namespace, relation, subjects, max_depth)[0]
-        ty = self.snapshot.type_id(namespace, relation)
-        targets = resolve_subjects(self.snapshot, list(subjects))
-        if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
-            return [[] for _ in targets]
-        return [self._objects(ids) for ids in self.lookup_ids(targets, ty)]
-
-    def ListObjects(self, namespace, relation, subject, max_depth=None, with_via=False):
-        return self.list_objects_batch(namespace, relation, [subject], max_depth, with_via)[0]
-
 
 def host_list_objects(snapshot, namespace, relation, subject):
     """ListObjects on the CPU (host_lookup)"""
@@ -1047,13 +1101,17 @@ def host_list_objects(snapshot, namespace, relation, subject):
 
 
 class HostLookup(_ObjectPages, _Paths, _HostCombine, _ObjectsCombined, _HostDepth, _ObjectsDepth, _HostVia,
-                 _ObjectsVia):
-    """Lookup's paged, path, combined, depth and via calls on the CPU: host_lookup's ascending
-    lists, sliced or combined, host_path's paths laid out as the device call lays them out,
-    host_lookup_depth's lists and host_lookup_via's"""
+                 _ObjectsVia, _ObjectLists):
+    """Lookup's full-list, paged, path, combined, depth and via calls on the CPU: host_lookup's
+    ascending lists, whole, sliced or combined, host_path's paths laid out as the device call lays
+    them out, host_lookup_depth's lists and host_lookup_via's"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def lookup_ids_raw(self, targets, type_id=TYPE_ANY, capacity=0, wide=False):
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        return _host_cursor([self._members(int(t), type_id) for t in targets], capacity)
 
     def _via_members(self, x, k, type_id):
         return host_lookup_via(self.snapshot, x, k, type_id)
@@ -1158,7 +1216,7 @@ def _subjects_of(snapshot, ids):
     return users + sets
 
 
-class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth, _SubjectsVia):
+class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth, _SubjectsVia, _SubjectLists):
     """device handle over a snapshot's forward rows"""
     ABI, OPTS, STATS = "subjects", L.SubjectsOpts, L.SubjectsStats
 
@@ -1178,52 +1236,30 @@ class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth, _Subje
         """one ketogpu_subjects_page_depth call (_page_depth_raw)"""
         return self._page_depth_raw(roots, max_depth, from_ids, cls, limit)
 
-    def subject_ids_raw(self, roots, cls=TYPE_ANY, capacity=0):
-        """one ketogpu_subjects_ids call (_ids_raw)"""
-        return self._ids_raw("ids", [roots], [int(cls)], capacity)
+    def subject_ids_raw(self, roots, cls=TYPE_ANY, capacity=0, wide=False):
+        """one ketogpu_subjects_ids call (_ids_raw); wide: one ketogpu_subjects_ids_wide call, the
+        same results with the large closures spread over the whole device"""
+        return self._ids_raw("ids_wide" if wide else "ids", [roots], [int(cls)], capacity)
 
-    def subject_ids(self, roots, cls=TYPE_ANY, capacity=None):
-        """-> one ascending uint32 array per root.  The first call uses `capacity` ids (default
-        64 per root); only the roots whose lists were truncated are issued again, with
-        capacity = what they need.  An id outside the snapshot raises EINVAL."""
-        roots = np.ascontiguousarray(roots, dtype=np.uint32)
-        return _all_lists(lambda idx, cap: self.subject_ids_raw(roots[idx], cls, cap), len(roots),
-                          64 * len(roots) if capacity is None else int(capacity), True,
-                          lambda k: f"root {int(roots[k])} is outside the snapshot")
+    def wide_stats(self):
+        return self._stats(L.WideStats(), "wide_stats_get")
 
     def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100):
         """one ketogpu_subjects_page call (_page_raw)"""
         return self._page_raw(roots, from_ids, cls, limit)
 
-    # ---- names
-    def list_subjects_batch(self, roots, kind="ids", max_depth=None, with_via=False):
-        """per (namespace, object, relation) root: the subjects s with Check(root@s), SubjectIDs
-        then SubjectSets, each sorted.  kind: "ids" (subject ids only), "any", or a
-        (namespace, relation) pair (subject sets of that type; an unknown pair lists nothing).
-        With max_depth: those within that many hops (list_subjects_depth_batch's lists); with_via:
-        (subject, via, hops) instead of subjects (list_subjects_via_batch)"""
-        if with_via:
-            return self.list_subjects_via_batch(roots, kind, max_depth)
-        if max_depth is not None:
-            return self.list_subjects_depth_batch(roots, max_depth, kind)[0]
-        roots = list(roots)
-        cls = _class_of_kind(self.snapshot, kind)
-        ids = resolve_roots(self.snapshot, roots)
-        if cls == TYPE_NONE:
-            return [[] for _ in roots]
-        return [_subjects_of(self.snapshot, v) for v in self.subject_ids(ids, cls)]
-
-    def ListSubjects(self, namespace, object, relation, kind="ids", max_depth=None, with_via=False):
-        return self.list_subjects_batch([(namespace, object, relation)], kind, max_depth, with_via)[0]
-
 
 class HostSubjects(_SubjectPages, _HostCombine, _SubjectsCombined, _HostDepth, _SubjectsDepth, _HostVia,
-                   _SubjectsVia):
-    """Subjects' paged, combined, depth and via calls on the CPU: host_subjects' ascending lists,
-    sliced or combined, host_subjects_depth's lists and host_subjects_via's"""
+                   _SubjectsVia, _SubjectLists):
+    """Subjects' full-list, paged, combined, depth and via calls on the CPU: host_subjects'
+    ascending lists, whole, sliced or combined, host_subjects_depth's lists and host_subjects_via's"""
 
     def __init__(self, snapshot):
         self.snapshot = snapshot
+
+    def subject_ids_raw(self, roots, cls=TYPE_ANY, capacity=0, wide=False):
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        return _host_cursor([self._members(int(r), cls) for r in roots], capacity)
 
     def _via_members(self, x, k, cls):
         return host_subjects_via(self.snapshot, x, k, cls)
