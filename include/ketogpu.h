@@ -444,6 +444,9 @@ int ketogpu_engine_wait(ketogpu_engine *e);
  * (KETOGPU_LABEL_TAIL), so this is below ketogpu_run_stats.full_requests of a
  * synchronized call over the same batch. */
 int ketogpu_engine_piped_full_requests(ketogpu_engine *e, uint64_t *out);
+/* diagnostics: plan label's first-stage launches on this engine so far in which a wave ran two
+ * units of 16 requests (KETOGPU_LABEL_PAIR) */
+int ketogpu_engine_label_pair_launches(ketogpu_engine *e, uint64_t *out);
 void ketogpu_queries_free(ketogpu_queries *q);
 
 /* statistics of the last run on this engine (for the roofline report) */
@@ -1566,6 +1569,11 @@ int ketogpu_device_count(void);
  * nothing else; *ms_per_launch averaged over `reps` launches on `device` (keto_amd/csrc/
  * probe.hip; bench.py's roofline.line_ceiling) */
 int ketogpu_probe_random_lines(int device, uint64_t table_bytes, uint64_t requests, int reps, double *ms_per_launch);
+/* the same kernel under the pipelined calls' conditions: `reps` launches round-robin over
+ * `streams` (1..8, else KETOGPU_EINVAL) non-blocking streams, timed from an event ahead of
+ * the first launch to one behind every stream's last; *ms_per_launch = that time / reps */
+int ketogpu_probe_random_lines_streams(int device, uint64_t table_bytes, uint64_t requests, int reps, int streams,
+                                       double *ms_per_launch);
 
 #ifdef __cplusplus
 }

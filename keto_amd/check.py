@@ -167,6 +167,12 @@ class Engine:
         L.check(self.L.ketogpu_engine_piped_full_requests(self.h, C.byref(n)))
         return n.value
 
+    def label_pair_launches(self):
+        """plan label's first-stage launches so far with two units per wave (KETOGPU_LABEL_PAIR)"""
+        n = C.c_uint64()
+        L.check(self.L.ketogpu_engine_label_pair_launches(self.h, C.byref(n)))
+        return n.value
+
     def set_events(self, every_kernel):
         """host-to-host batches: a timing event between the call's kernels (main_ms = the
         first stage's own time) or only around the call (default)"""

@@ -2690,19 +2690,19 @@ __device__ __forceinline__ bool label_lookup(const uint32_t *row, uint32_t x) {
 // settled: it is not listed in F, whether it hit or not.  A wave without one skips the phase
 // (one ballot).  The synchronized and host paths keep TAIL = false: their statistics
 // (full_requests, the entries counter) are pinned to the first stage as it was.
-template <int HS, int HP, bool TAIL = false>
-__device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelGraph &L, uint32_t r_lane,
-                                           uint32_t t_lane, uint64_t *allowed, const uint64_t unit,
-                                           const LabelRest &R, const LabelRest &F, unsigned long long *stats) {
-    static_assert((HS == 8 || HS == 16 || HS == 32 || HS == 64) && (HP == 8 || HP == 16 || HP == 32 || HP == 64),
-                  "heads of 8, 16, 32 or 64 words");
-    constexpr int SW = HS / 4, PW = HP / 4;                                   // head words per lane
-    constexpr uint32_t CS = HS - kHeadFixed, CP = HP - kHeadFixed;            // inline entries
-    const uint32_t lane = threadIdx.x & 63, q = lane >> 2, sub = lane & 3;
-    const uint32_t r = (uint32_t)__shfl((int)r_lane, (int)q, 64), t = (uint32_t)__shfl((int)t_lane, (int)q, 64);
-    const bool some = r != KETOGPU_NODE_NONE && t != KETOGPU_NODE_NONE;
-    const bool valid = some && r < kDynBase;
-    uint32_t sw[SW], pw[PW];
+//
+// The unit is written in two steps, label_heads (the head reads, issued) and label_settle
+// (everything that consumes them): label_unit runs them back to back, label_pair issues two
+// units' reads before it settles either.
+
+// this lane's words of request q's two heads (r, t: the request's ids on its four lanes),
+// pads where the request reads none
+template <int HS, int HP>
+__device__ __forceinline__ void label_heads(const LabelGraph &L, uint32_t r, uint32_t t, uint32_t (&sw)[HS / 4],
+                                            uint32_t (&pw)[HP / 4]) {
+    constexpr int SW = HS / 4, PW = HP / 4;  // head words per lane
+    const uint32_t sub = threadIdx.x & 3;
+    const bool valid = r != KETOGPU_NODE_NONE && t != KETOGPU_NODE_NONE && r < kDynBase;
 #pragma unroll
     for (int k = 0; k < SW; k++) sw[k] = 0xFFFFFFFFu;
 #pragma unroll
@@ -2711,6 +2711,20 @@ __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelG
         label_head_load<SW>(L.S + (uint64_t)t * HS, sub, sw);
         label_head_load<PW>(L.P + (uint64_t)r * HP, sub, pw);
     }
+}
+
+template <int HS, int HP, bool TAIL>
+__device__ __forceinline__ void label_settle(LabelShared<HS, HP> &sh, const LabelGraph &L, const uint32_t r,
+                                             const uint32_t t, const uint32_t (&sw)[HS / 4],
+                                             const uint32_t (&pw)[HP / 4], uint64_t *allowed, const uint64_t unit,
+                                             const LabelRest &R, const LabelRest &F, unsigned long long *stats) {
+    static_assert((HS == 8 || HS == 16 || HS == 32 || HS == 64) && (HP == 8 || HP == 16 || HP == 32 || HP == 64),
+                  "heads of 8, 16, 32 or 64 words");
+    constexpr int SW = HS / 4, PW = HP / 4;                                   // head words per lane
+    constexpr uint32_t CS = HS - kHeadFixed, CP = HP - kHeadFixed;            // inline entries
+    const uint32_t lane = threadIdx.x & 63, q = lane >> 2, sub = lane & 3;
+    const bool some = r != KETOGPU_NODE_NONE && t != KETOGPU_NODE_NONE;
+    const bool valid = some && r < kDynBase;
     const uint32_t ns = label_word<SW, 0>(sw), np = label_word<PW, 0>(pw);
     const bool labelled = valid && ns != kNoLabel && np != kNoLabel;
     const uint64_t smask = (uint64_t)label_word<SW, 2>(sw) | (uint64_t)label_word<SW, 3>(sw) << 32;
@@ -2874,6 +2888,56 @@ __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelG
     }
 }
 
+// one unit; r_lane, t_lane: request j's ids on lane j < 16
+template <int HS, int HP, bool TAIL = false>
+__device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelGraph &L, uint32_t r_lane,
+                                           uint32_t t_lane, uint64_t *allowed, const uint64_t unit,
+                                           const LabelRest &R, const LabelRest &F, unsigned long long *stats) {
+    const uint32_t q = (threadIdx.x & 63) >> 2;
+    const uint32_t r = (uint32_t)__shfl((int)r_lane, (int)q, 64), t = (uint32_t)__shfl((int)t_lane, (int)q, 64);
+    uint32_t sw[HS / 4], pw[HP / 4];
+    label_heads<HS, HP>(L, r, t, sw, pw);
+    label_settle<HS, HP, TAIL>(sh, L, r, t, sw, pw, allowed, unit, R, F, stats);
+}
+
+// Two consecutive units (`unit` even, and unit + 1 where `two`) by one wave
+// (KETOGPU_LABEL_PAIR).  A unit's requests are 64 bytes of `roots` and 64 of `targets`:
+// half a 128-byte line of each, so with a wave per unit every request line is fetched by two
+// workgroups, which the dispatcher hands to different XCDs — the line crosses the fabric
+// twice.  Here lanes 0-31 read roots[16 unit .. 16 unit + 31] and lanes 32-63 the same range
+// of targets in ONE wave instruction: two whole lines, each fetched by this wave alone
+// (requests at or past n read as NONE).  Both units' head reads are issued before either is
+// consumed, so the wave has twice a unit's lines in flight; then the units are settled one
+// after the other exactly as label_unit settles one (unit number, shard, records, result part
+// and statistics are per unit), both in the one image — the second unit's heads wait in
+// registers — so a CU holds as many waves as with a unit per wave (two images would halve
+// them at 32-word heads: LDS).  Without `two` (the last unit has no partner) the second unit
+// is neither read nor written.
+template <int HS, int HP, bool TAIL>
+__device__ __forceinline__ void label_pair(LabelShared<HS, HP> &sh, const LabelGraph &L, const uint32_t *roots,
+                                           const uint32_t *targets, uint64_t n, uint64_t *allowed,
+                                           const uint64_t unit, const bool two, const LabelRest &R,
+                                           const LabelRest &F, unsigned long long *stats) {
+    const uint32_t lane = threadIdx.x & 63, q = lane >> 2;
+    const uint64_t c = unit * 16 + (lane & 31);
+    uint32_t v = KETOGPU_NODE_NONE;
+    if (c < n) v = (lane < 32 ? roots : targets)[c];
+    const uint32_t r0 = (uint32_t)__shfl((int)v, (int)q, 64), t0 = (uint32_t)__shfl((int)v, (int)(32 + q), 64);
+    uint32_t r1 = KETOGPU_NODE_NONE, t1 = KETOGPU_NODE_NONE;
+    if (two) {  // (wave-uniform)
+        r1 = (uint32_t)__shfl((int)v, (int)(16 + q), 64);
+        t1 = (uint32_t)__shfl((int)v, (int)(48 + q), 64);
+    }
+    uint32_t sw0[HS / 4], pw0[HP / 4], sw1[HS / 4], pw1[HP / 4];
+    label_heads<HS, HP>(L, r0, t0, sw0, pw0);
+    label_heads<HS, HP>(L, r1, t1, sw1, pw1);
+    label_settle<HS, HP, TAIL>(sh, L, r0, t0, sw0, pw0, allowed, unit, R, F, stats);
+    if (two) {
+        wave_sync();  // (the first unit's reads of the image are behind)
+        label_settle<HS, HP, TAIL>(sh, L, r1, t1, sw1, pw1, allowed, unit + 1, R, F, stats);
+    }
+}
+
 // the next call's list counters (rest and full), cleared by wave 0 of workgroup 0
 __device__ __forceinline__ void label_clear_next(const LabelRest &R, const LabelRest &F) {
     if (blockIdx.x == 0 && threadIdx.x < 64) {  // 64 lanes: every shard
@@ -2882,17 +2946,28 @@ __device__ __forceinline__ void label_clear_next(const LabelRest &R, const Label
     }
 }
 
-template <int HS, int HP>
+// PAIR: workgroup b runs units unit0 + 2 b and unit0 + 2 b + 1 (label_pair; unit0 even, and
+// the launch's last workgroup lacks a partner only at the batch's last unit: launch_bidi).
+// Launched only with KETOGPU_LABEL_PAIR=2: alone on the chip the paired launch is slower.
+template <int HS, int HP, bool PAIR = false>
 __global__ __launch_bounds__(64) void label_kernel(LabelGraph L, const uint32_t *roots, const uint32_t *targets,
                                                    uint64_t n, uint64_t *allowed, LabelRest R, LabelRest F,
                                                    unsigned long long *stats, uint64_t unit0) {
     __shared__ LabelShared<HS, HP> sh;
     if (unit0 == 0) label_clear_next(R, F);
     const uint64_t units = (n + 15) / 16;
-    const uint64_t unit = unit0 + blockIdx.x;
-    uint32_t r, t;
-    bidi_load_rt<16>(unit, units, roots, targets, n, r, t);
-    label_unit<HS, HP>(sh, L, r, t, allowed, unit, R, F, stats);
+    uint64_t unit;  // the last unit of this workgroup
+    if constexpr (PAIR) {
+        unit = unit0 + 2 * (uint64_t)blockIdx.x;
+        const bool two = unit + 1 < units;
+        label_pair<HS, HP, false>(sh, L, roots, targets, n, allowed, unit, two, R, F, stats);
+        unit += two;
+    } else {
+        unit = unit0 + blockIdx.x;
+        uint32_t r, t;
+        bidi_load_rt<16>(unit, units, roots, targets, n, r, t);
+        label_unit<HS, HP>(sh, L, r, t, allowed, unit, R, F, stats);
+    }
     // the last result word's 16-bit parts past the last unit (no unit writes them)
     if (unit + 1 == units && threadIdx.x == 0)
         for (uint64_t u = units; u < (units + 3) / 4 * 4; u++) reinterpret_cast<uint16_t *>(allowed)[u] = 0;
@@ -3132,7 +3207,9 @@ __global__ __launch_bounds__(64) void label_full_kernel(LabelGraph L, uint64_t *
 // the kernel holds as many workgroups per CU as label_kernel does.  TAIL: the first stage
 // settles short P overflows itself (label_unit's tail phase), so the next launch's dense
 // role finds about a sixth of the records (config #2).
-template <int HS, int HP, bool TAIL>
+// PAIR: workgroup D + b is units 2 b and 2 b + 1 (label_pair), so the grid is
+// D + ceil(units / 2).
+template <int HS, int HP, bool TAIL, bool PAIR = false>
 __global__ __launch_bounds__(64) void label_carry_kernel(LabelGraph L, const uint32_t *roots, const uint32_t *targets,
                                                          uint64_t n, uint64_t *allowed, LabelRest R, LabelRest F,
                                                          LabelRest Fd, uint64_t *allowed_d, uint32_t D) {
@@ -3148,10 +3225,18 @@ __global__ __launch_bounds__(64) void label_carry_kernel(LabelGraph L, const uin
         F.next_count[threadIdx.x * kRestStride] = 0u;
     }
     const uint64_t units = (n + 15) / 16;
-    const uint64_t unit = blockIdx.x - D;
-    uint32_t r, t;
-    bidi_load_rt<16>(unit, units, roots, targets, n, r, t);
-    label_unit<HS, HP, TAIL>(sh, L, r, t, allowed, unit, R, F, nullptr);
+    uint64_t unit;  // the last unit of this workgroup
+    if constexpr (PAIR) {
+        unit = 2 * (uint64_t)(blockIdx.x - D);
+        const bool two = unit + 1 < units;
+        label_pair<HS, HP, TAIL>(sh, L, roots, targets, n, allowed, unit, two, R, F, nullptr);
+        unit += two;
+    } else {
+        unit = blockIdx.x - D;
+        uint32_t r, t;
+        bidi_load_rt<16>(unit, units, roots, targets, n, r, t);
+        label_unit<HS, HP, TAIL>(sh, L, r, t, allowed, unit, R, F, nullptr);
+    }
     // the last result word's 16-bit parts past the last unit (no unit writes them)
     if (unit + 1 == units && threadIdx.x == 0)
         for (uint64_t u = units; u < (units + 3) / 4 * 4; u++) reinterpret_cast<uint16_t *>(allowed)[u] = 0;
@@ -4868,6 +4953,20 @@ struct ketogpu_engine {
         const char *e = getenv("KETOGPU_LABEL_TAIL");
         return !e || atoi(e) != 0;
     }();
+    // KETOGPU_LABEL_PAIR: a first-stage wave runs two consecutive units, whose requests it
+    // reads as two whole lines (label_pair).  1 (default): in the launches where that was
+    // measured to gain — queued calls (label_carry_kernel) at 32-word heads.  A synchronized
+    // call's label_kernel, one launch alone on the chip, is 5% slower paired (0.0487 against
+    // 0.0463 ms at 10^6 config #2 requests, profiles/r10/full_ab.jsonl), and the other head
+    // pairs are not measured yet.  2: every label_kernel and label_carry_kernel launch
+    // (measurements and tests).  0: none.
+    int label_pair_mode = [] {
+        const char *e = getenv("KETOGPU_LABEL_PAIR");
+        return e ? atoi(e) : 1;
+    }();
+    bool pair_carry() const { return label_pair_mode >= 2 || (label_pair_mode == 1 && label_hs == 32 && label_hp == 32); }
+    bool pair_sync() const { return label_pair_mode >= 2; }
+    uint64_t pair_launches = 0;  // launches with two units per wave (ketogpu_engine_label_pair_launches)
     // the requests the most recent flushed pass of a queued call found listed: queued calls
     // list fewer than synchronized ones (the tail phase), so their passes are sized by their
     // own count.  label_full_kernel writes its list's total into the host-mapped mirror; it
@@ -5018,9 +5117,20 @@ struct ketogpu_engine {
                      unsigned long long *stp, uint64_t unit0 = 0, hipStream_t stream = nullptr, bool chunked = false) {
         if (!stream) stream = this->stream;
         if (c.lite == 3) {  // plan label: 2-hop labels, plan lite for requests without
+            // two units per wave where the launch's units pair up: an even first unit, and an
+            // odd count only where the launch ends the batch (a chunk is a multiple of 64 requests:
+            // pipe_chunk; any other launch runs one unit per wave)
+            const bool pair = pair_sync() && unit0 % 2 == 0 && (grid % 2 == 0 || unit0 + grid == (q.n + 15) / 16);
+            pair_launches += pair;
             label_dispatch([&](auto hs, auto hp) {
-                KLAUNCH((label_kernel<decltype(hs)::value, decltype(hp)::value>), dim3(grid), dim3(64), pad, stream,
-                        lgraph, q.roots, q.targets, q.n, q.allowed, label_rest(q.n), label_full(q.n), stats, unit0);
+                if (pair)
+                    KLAUNCH((label_kernel<decltype(hs)::value, decltype(hp)::value, true>), dim3((grid + 1) / 2),
+                            dim3(64), pad, stream, lgraph, q.roots, q.targets, q.n, q.allowed, label_rest(q.n),
+                            label_full(q.n), stats, unit0);
+                else
+                    KLAUNCH((label_kernel<decltype(hs)::value, decltype(hp)::value>), dim3(grid), dim3(64), pad,
+                            stream, lgraph, q.roots, q.targets, q.n, q.allowed, label_rest(q.n), label_full(q.n),
+                            stats, unit0);
             });
             return;
         }
@@ -5201,7 +5311,9 @@ struct ketogpu_engine {
     int32_t request_path = 0;
     hipStream_t copy_stream = nullptr, stream2 = nullptr;
     unsigned long long *d_bad = nullptr;  // smallest request index with an id outside the snapshot
-    uint64_t pipe_chunk = 1 << 18;        // requests per pipelined chunk (KETOGPU_PIPE_CHUNK)
+    uint64_t pipe_chunk = 1 << 18;        // requests per pipelined chunk (KETOGPU_PIPE_CHUNK), kept a multiple of 64:
+                                          // chunks begin at whole result words, and launch_bidi pairs a chunk's
+                                          // units (label_pair) only while they begin at an even unit
     // pinned requests read in place by one first-stage launch (bidi_host_kernel);
     // KETOGPU_PIPE_MODE=chunks restores the chunk pipeline (load_kernel + a launch per chunk)
     bool pipe_direct = true;
@@ -6522,15 +6634,19 @@ struct ketogpu_engine {
                     pend[cur_pipe] = PendingDense{};
                     const unsigned D = p.on ? piped_grid() : 0u;
                     label_dispatch([&](auto hs, auto hp) {
-                        if (label_tail)
-                            KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value, true>),
-                                    dim3(D + (unsigned)bunits), dim3(64), lds_pad, stream, lgraph, q.roots, q.targets,
-                                    q.n, q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D);
-                        else
-                            KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value, false>),
-                                    dim3(D + (unsigned)bunits), dim3(64), lds_pad, stream, lgraph, q.roots, q.targets,
-                                    q.n, q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D);
+                        auto go = [&](auto tail, auto pair) {
+                            const unsigned first = (unsigned)(decltype(pair)::value ? (bunits + 1) / 2 : bunits);
+                            KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value,
+                                                        decltype(tail)::value, decltype(pair)::value>),
+                                    dim3(D + first), dim3(64), lds_pad, stream, lgraph, q.roots, q.targets, q.n,
+                                    q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D);
+                        };
+                        if (label_tail && pair_carry()) go(std::true_type{}, std::true_type{});
+                        else if (label_tail) go(std::true_type{}, std::false_type{});
+                        else if (pair_carry()) go(std::false_type{}, std::true_type{});
+                        else go(std::false_type{}, std::false_type{});
                     });
+                    pair_launches += pair_carry();
                     if (p.q) p.q->pass = 2;
                 } else if (!src) {
                     launch_bidi(bidi_cfg, (unsigned)bunits, lds_pad, q, nullptr, nullptr, list[0], &spill_count[0],
@@ -7447,6 +7563,14 @@ int ketogpu_engine_piped_full_requests(ketogpu_engine *e, uint64_t *out) {
     if (!e || !out) throw Error(KETOGPU_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
     *out = e->piped_full_known ? e->piped_full : 0;
+    API_END
+}
+
+int ketogpu_engine_label_pair_launches(ketogpu_engine *e, uint64_t *out) {
+    API_BEGIN
+    if (!e || !out) throw Error(KETOGPU_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    *out = e->pair_launches;
     API_END
 }
 

@@ -35,25 +35,33 @@ __global__ __launch_bounds__(64) void probe_lines_kernel(const uint32_t *table, 
 
 }  // namespace
 
-extern "C" int ketogpu_probe_random_lines(int device, uint64_t table_bytes, uint64_t requests, int reps,
-                                          double *ms_per_launch) {
-    if (!ms_per_launch || requests == 0 || reps <= 0 || table_bytes < (1u << 20)) return KETOGPU_EINVAL;
+// `reps` launches round-robin over `streams` non-blocking streams, timed from an event ahead
+// of the first launch (every stream waits for it) to one behind the last launch of every stream
+extern "C" int ketogpu_probe_random_lines_streams(int device, uint64_t table_bytes, uint64_t requests, int reps,
+                                                  int streams, double *ms_per_launch) {
+    constexpr int kMaxStreams = 8;
+    if (!ms_per_launch || requests == 0 || reps <= 0 || table_bytes < (1u << 20) || streams < 1 ||
+        streams > kMaxStreams)
+        return KETOGPU_EINVAL;
     *ms_per_launch = 0;
     if (hipSetDevice(device) != hipSuccess) return KETOGPU_EDEVICE;
     const uint64_t lines = table_bytes / 128;
     uint32_t *table = nullptr, *rq = nullptr;
-    uint16_t *out = nullptr;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    uint16_t *out = nullptr;  // a result array per stream
+    hipStream_t s[kMaxStreams] = {};
+    hipEvent_t e0 = nullptr, e1 = nullptr, end[kMaxStreams] = {};
     int rc = KETOGPU_OK;
     auto ok = [&](hipError_t e) {
         if (e != hipSuccess && rc == KETOGPU_OK) rc = e == hipErrorOutOfMemory ? KETOGPU_ENOMEM : KETOGPU_EDEVICE;
         return rc == KETOGPU_OK;
     };
     const uint64_t grid = (requests + 15) / 16;
-    if (ok(hipMalloc(&table, lines * 128)) && ok(hipMalloc(&rq, 8 * requests)) && ok(hipMalloc(&out, 2 * grid)) &&
-        ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) && ok(hipEventCreate(&e0)) && ok(hipEventCreate(&e1)) &&
-        ok(hipMemsetAsync(table, 0x5a, lines * 128, s))) {
+    for (int k = 0; k < streams && rc == KETOGPU_OK; k++)
+        if (ok(hipStreamCreateWithFlags(&s[k], hipStreamNonBlocking)))
+            ok(hipEventCreateWithFlags(&end[k], hipEventDisableTiming));
+    if (rc == KETOGPU_OK && ok(hipMalloc(&table, lines * 128)) && ok(hipMalloc(&rq, 8 * requests)) &&
+        ok(hipMalloc(&out, 2 * grid * streams)) && ok(hipEventCreate(&e0)) && ok(hipEventCreate(&e1)) &&
+        ok(hipMemsetAsync(table, 0x5a, lines * 128, s[0]))) {
         // random request ids (xorshift on the host: the same sequence every run)
         uint32_t *h = nullptr;
         if (ok(hipHostMalloc(&h, 8 * requests, hipHostMallocDefault))) {
@@ -62,27 +70,43 @@ extern "C" int ketogpu_probe_random_lines(int device, uint64_t table_bytes, uint
                 x ^= x << 13, x ^= x >> 7, x ^= x << 17;
                 h[k] = (uint32_t)(x >> 17);
             }
-            if (ok(hipMemcpyAsync(rq, h, 8 * requests, hipMemcpyHostToDevice, s)) && ok(hipStreamSynchronize(s))) {
-                for (int k = 0; k < 3 && rc == KETOGPU_OK; k++)
-                    probe_lines_kernel<<<dim3((unsigned)grid), dim3(64), 0, s>>>(table, lines, rq, requests, out);
+            auto launch = [&](int k) {
+                probe_lines_kernel<<<dim3((unsigned)grid), dim3(64), 0, s[k % streams]>>>(table, lines, rq, requests,
+                                                                                          out + grid * (k % streams));
+            };
+            if (ok(hipMemcpyAsync(rq, h, 8 * requests, hipMemcpyHostToDevice, s[0])) && ok(hipStreamSynchronize(s[0]))) {
+                for (int k = 0; k < 3 * streams && rc == KETOGPU_OK; k++) launch(k);
                 ok(hipGetLastError());
-                if (ok(hipEventRecord(e0, s))) {
-                    for (int k = 0; k < reps && rc == KETOGPU_OK; k++)
-                        probe_lines_kernel<<<dim3((unsigned)grid), dim3(64), 0, s>>>(table, lines, rq, requests, out);
+                for (int k = 1; k < streams; k++) ok(hipStreamSynchronize(s[k]));
+                if (ok(hipEventRecord(e0, s[0]))) {
+                    for (int k = 1; k < streams; k++) ok(hipStreamWaitEvent(s[k], e0, 0));
+                    for (int k = 0; k < reps && rc == KETOGPU_OK; k++) launch(k);
                     ok(hipGetLastError());
+                    for (int k = 1; k < streams; k++)
+                        if (ok(hipEventRecord(end[k], s[k]))) ok(hipStreamWaitEvent(s[0], end[k], 0));
                     float ms = 0;
-                    if (ok(hipEventRecord(e1, s)) && ok(hipEventSynchronize(e1)) && ok(hipEventElapsedTime(&ms, e0, e1)))
+                    if (ok(hipEventRecord(e1, s[0])) && ok(hipEventSynchronize(e1)) && ok(hipEventElapsedTime(&ms, e0, e1)))
                         *ms_per_launch = ms / reps;
                 }
             }
             (void)hipHostFree(h);
         }
     }
-    if (s) (void)hipStreamSynchronize(s);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (s) (void)hipStreamDestroy(s);
+    for (int k = 0; k < streams; k++)
+        if (s[k]) (void)hipStreamSynchronize(s[k]);
+    for (hipEvent_t e : {e0, e1})
+        if (e) (void)hipEventDestroy(e);
+    for (int k = 0; k < streams; k++) {
+        if (end[k]) (void)hipEventDestroy(end[k]);
+        if (s[k]) (void)hipStreamDestroy(s[k]);
+    }
     for (void *p : {(void *)table, (void *)rq, (void *)out})
         if (p) (void)hipFree(p);
     return rc;
+}
+
+// one launch at a time on one stream (bench.py's roofline.line_ceiling)
+extern "C" int ketogpu_probe_random_lines(int device, uint64_t table_bytes, uint64_t requests, int reps,
+                                          double *ms_per_launch) {
+    return ketogpu_probe_random_lines_streams(device, table_bytes, requests, reps, 1, ms_per_launch);
 }
