@@ -1556,6 +1556,37 @@ int ketogpu_subjects_ids_wide(ketogpu_subjects *h, const uint32_t *roots, size_t
                               uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
 int ketogpu_lookup_ids_wide(ketogpu_lookup *l, const uint32_t *targets, size_t n, uint32_t type, uint32_t *out,
                             uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed);
+/* The depth-limited and the paged calls with the same replacement (DESIGN.md "Chip-wide pages and
+ * depths").  ketogpu_*_ids_depth_wide follows ketogpu_*_ids_depth word for word, ketogpu_*_page_wide
+ * follows ketogpu_*_page_depth word for word: the same member sets M_k(x), frontier, counts, page
+ * rules (ascending by node id; from / returned / remaining; KETOGPU_PAGE_INVALID; the limit
+ * checks; no truncation protocol), argument checks and INVALID / NONE / never-expanded
+ * classification.  A NULL max_depth array, or KETOGPU_DEPTH_ALL, is no limit: a paged call without
+ * a limit is ketogpu_*_page_wide with max_depth NULL, and answers what ketogpu_*_page answers.
+ * from and frontier may be NULL.  The depth tier-1 kernels run unchanged and a request overflows
+ * exactly as in the depth calls; the overflows run in rounds of the wide tier, whose level L is
+ * its launch L: a request with the limit k appends nothing after launch k.  A page is selected
+ * by one workgroup per request; the bitmap is then cleared, and the members below `from`
+ * counted, by one workgroup per tile of ketogpu_wide_clear_tile_ids() ids.  These calls count in
+ * ketogpu_wide_stats alone (ids_produced: the sum of `returned` for pages; truncated_lists moves
+ * only in the full-list calls); ketogpu_depth_stats does not move.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+int ketogpu_subjects_ids_depth_wide(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth, size_t n,
+                                    uint32_t cls, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                                    uint64_t *frontier, uint64_t *needed);
+int ketogpu_lookup_ids_depth_wide(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth, size_t n,
+                                  uint32_t type, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                                  uint64_t *frontier, uint64_t *needed);
+int ketogpu_subjects_page_wide(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth,
+                               const uint32_t *from, size_t n, uint32_t cls, uint32_t limit,
+                               uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
+                               uint64_t *remaining, uint64_t *frontier);
+int ketogpu_lookup_page_wide(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth,
+                             const uint32_t *from, size_t n, uint32_t type, uint32_t limit,
+                             uint32_t *out /* n * limit words */, uint32_t *returned, uint64_t *count,
+                             uint64_t *remaining, uint64_t *frontier);
+/* ids one workgroup of the paged finish's clear kernel covers */
+uint32_t ketogpu_wide_clear_tile_ids(void);
 
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);

@@ -607,6 +607,13 @@ SIGNATURES = {
     "ketogpu_lookup_wide_stats_get": (C.c_int, [vp, C.POINTER(WideStats)]),
     "ketogpu_subjects_ids_wide": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
     "ketogpu_lookup_ids_wide": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_subjects_ids_depth_wide": (C.c_int, [vp, vp, vp, sz, u32, vp, C.c_uint64, vp, vp, vp,
+                                                  C.POINTER(C.c_uint64)]),
+    "ketogpu_lookup_ids_depth_wide": (C.c_int, [vp, vp, vp, sz, u32, vp, C.c_uint64, vp, vp, vp,
+                                                C.POINTER(C.c_uint64)]),
+    "ketogpu_subjects_page_wide": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp]),
+    "ketogpu_lookup_page_wide": (C.c_int, [vp, vp, vp, vp, sz, u32, u32, vp, vp, vp, vp, vp]),
+    "ketogpu_wide_clear_tile_ids": (u32, []),
 }
 
 _lib = None

@@ -4,7 +4,7 @@
 // overflow count, tier 2 in rounds of `slots`, the copies back) and the shared parts of their
 // ABI entry points, and how a handle follows in-place writes: the patched refresh (try_patch,
 // list_patch_kernel) with the full upload as its fallback, and the wide tier's state and round
-// (wide.hpp: need_wide_slots, wide_round, run_wide).  A handle adds its graph struct, its
+// (wide.hpp: need_wide_slots, wide_round, run_wide, run_page_wide).  A handle adds its graph struct, its
 // upload, what the patched refresh asks of it, its launches (passed to the drivers as callables)
 // and its statistics.
 #pragma once
@@ -488,7 +488,8 @@ struct ListHandle {
     // words, and its counters; all of it counted against the budget, so a wide round may have
     // fewer slots.  The queue is allocated again when col_words moved (an upload with more
     // edges); drop_tier2 drops it when (bound, Ni) move.  Neither is ever cleared: the tail says
-    // which items hold, and a round zeroes its counters itself.
+    // which items hold, and a round zeroes its counters itself, the paged finish's `below` word
+    // per slot among them (wide::round_words: full-list and paged rounds share this state).
     template <class Need>
     uint32_t need_wide_slots(uint32_t wanted, uint64_t words, Need &&need) {
         if (col_words != wide_col_words) wide_slots = 0, wide_slot_max = 0;
@@ -498,7 +499,7 @@ struct ListHandle {
         wide_slots = 0;
         k = std::min<uint64_t>(k, need((uint32_t)k));  // (at least one)
         wide_qcap = wide::queue_items(k, g.Ni, col_words);
-        d_wq.need(wide_qcap), d_wctr.need(wide::ctr_words(k)), h_wtail.need(wide::kHead);
+        d_wq.need(wide_qcap), d_wctr.need(wide::round_words(k)), h_wtail.need(wide::kHead);
         wide_col_words = col_words;
         return wide_slots = (uint32_t)k;
     }
@@ -511,17 +512,20 @@ struct ListHandle {
     }
 
     // One round of the wide tier: the requests d_ovf[first .. first + k) with slots 0 .. k - 1.
-    // rows: the ids below it have a row.  level(w, lb, le) launches the handle's level kernel
-    // over the items [lb, le), write(w) its write kernel; seed and reservation are wide.hpp's own.
-    // A queue that proved too small fails the call before anything is written, bitmaps zeroed.
-    template <class Level, class Write>
-    void wide_round(uint32_t first, uint32_t k, uint32_t rows, uint64_t capacity, Level &&level, Write &&write) {
+    // rows: the ids below it have a row.  level(w, L, lb, le) launches the handle's level kernel
+    // over the items [lb, le) as launch L of the round (1-based: the members at distance L);
+    // finish(w) is either wide_reserve and the handle's write kernel or wide_page_finish.  The
+    // seed is wide.hpp's own.  A depth call's frontier words are zero before the seed
+    // (upload_depth; tier 1 writes only those of the requests it answers).  A queue that proved
+    // too small fails the call before anything is written, bitmaps zeroed.
+    template <class Level, class Finish>
+    void wide_round(uint32_t first, uint32_t k, uint32_t rows, Level &&level, Finish &&finish) {
         const wide::State w{d_bm.p, bm_words, d_wq.p, wide_qcap, d_wctr.p, k, rows};
-        HIP_CHECK(hipMemsetAsync(d_wctr.p, 0, wide::ctr_words(k) * 8, stream));
+        HIP_CHECK(hipMemsetAsync(d_wctr.p, 0, wide::round_words(k) * 8, stream));
         KLAUNCH(wide::seed_kernel, dim3(k), dim3(64), 0, stream, g, d_req.p, d_ovf.p, first, w);
         unsigned long long lb = 0, le = wide_tail();
-        while (lb < le && !h_wtail.p[wide::kError]) {
-            level(w, lb, le);
+        for (uint32_t L = 1; lb < le && !h_wtail.p[wide::kError]; L++) {
+            level(w, L, lb, le);
             wst.levels++, wst.items += le - lb;
             lb = le, le = wide_tail();
         }
@@ -530,13 +534,33 @@ struct ListHandle {
             HIP_CHECK(hipStreamSynchronize(stream));
             throw Error(KETOGPU_EDEVICE, what + ": the wide tier's queue is too small for this round");
         }
-        KLAUNCH(wide::reserve_kernel, dim3((k + 63) / 64), dim3(64), 0, stream, d_ovf.p, first, w, list_out(capacity));
-        write(w);
+        finish(w);
+    }
+
+    // the full-list finish's first half: every slot's count reserved for its request
+    void wide_reserve(const wide::State &w, uint32_t first, uint64_t capacity) {
+        KLAUNCH(wide::reserve_kernel, dim3((w.nslots + 63) / 64), dim3(64), 0, stream, d_ovf.p, first, w,
+                list_out(capacity));
     }
 
     // the write kernel's grid: a workgroup per tile of one slot's bitmap
     dim3 wide_write_grid(uint32_t k) const {
         return dim3((unsigned)std::max<uint64_t>((bm_words + wide::kTile - 1) / wide::kTile, 1), k);
+    }
+
+    // ... and the paged finish's clear kernel's
+    dim3 wide_clear_grid(uint32_t k) const {
+        return dim3((unsigned)std::max<uint64_t>((bm_words + wide::kClearTile - 1) / wide::kClearTile, 1), k);
+    }
+
+    // the paged finish: select(w) and clear(w) launch the handle's kernels, each in a launch of
+    // its own (the clear kernel stores over what the select reads); the report is wide.hpp's own
+    template <class Select, class Clear>
+    void wide_page_finish(const wide::State &w, uint32_t first, uint32_t limit, Select &&select, Clear &&clear) {
+        select(w);
+        clear(w);
+        KLAUNCH(wide::page_final_kernel, dim3((w.nslots + 63) / 64), dim3(64), 0, stream, d_ovf.p, first, w,
+                page_out(limit));
     }
 
     // a wide call, counted in wst: run_cursor with rounds of the wide tier in tier 2's place.
@@ -552,6 +576,21 @@ struct ListHandle {
         wst.requests += c.requests, wst.tier1_requests += c.tier1_requests, wst.wide_requests += c.tier2_requests;
         wst.wide_rounds += c.tier2_rounds, wst.ids_produced += c.ids_produced;
         wst.truncated_lists += c.truncated_lists;
+        wst.last_call_ms = ms_of_call();
+    }
+
+    // a wide paged call, counted in wst: run_page with rounds of the wide tier in tier 2's
+    // place.  need and round as in run_wide; a page truncates nothing
+    template <class T1, class Need, class Round>
+    void run_page_wide(const uint32_t *req, const uint32_t *from, size_t n, uint32_t limit, uint32_t *out,
+                       uint32_t *returned, uint64_t *count, uint64_t *remaining, T1 &&tier1, Need &&need,
+                       Round &&round) {
+        struct {  // (what run_page counts, under tier 2's names)
+            uint64_t requests = 0, tier1_requests = 0, tier2_requests = 0, tier2_rounds = 0, ids_produced = 0;
+        } c;
+        run_page(c, req, from, n, limit, out, returned, count, remaining, tier1, need, round, [](Tally &) {});
+        wst.requests += c.requests, wst.tier1_requests += c.tier1_requests, wst.wide_requests += c.tier2_requests;
+        wst.wide_rounds += c.tier2_rounds, wst.ids_produced += c.ids_produced;
         wst.last_call_ms = ms_of_call();
     }
 

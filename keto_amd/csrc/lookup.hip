@@ -30,7 +30,10 @@
 // and a level per first visit.
 //
 // The wide call (ketogpu_lookup_ids_wide) is the full-list call with tier 1's overflows run by
-// wide.hpp's level-synchronous tier, spread over the whole device, instead of tier 2.
+// wide.hpp's level-synchronous tier, spread over the whole device, instead of tier 2.  The wide
+// depth and paged calls (ketogpu_lookup_ids_depth_wide / _page_wide) are the depth calls with the
+// same replacement: level L of the wide tier is its launch L, and the paged finish is wide.hpp's
+// select, clear and report.
 //
 // Every index is validated before it is used: targets against num_nodes before rev_off is
 // touched, row entries against num_expandable before the type array or a bitmap is.
@@ -539,6 +542,30 @@ __global__ __launch_bounds__(wide::kBlock) void lookup_wide_write_kernel(Rows g,
     wide::write(w, o, &s_cnt, &s_at, [&](uint32_t u) { return type_ok(g, u, type); });
 }
 
+// ketogpu_lookup_ids_depth_wide / _page_wide: the level under a depth limit, and the paged
+// finish's select and clear (wide.hpp "depth", "page")
+__global__ __launch_bounds__(wide::kBlock) void lookup_wide_level_depth_kernel(Rows g, uint32_t type, wide::State w,
+                                                                               unsigned long long lb,
+                                                                               unsigned long long le, wide::Cut cut) {
+    wide::level_depth(
+        g, g.Nx, w, lb, le, cut, [&](uint32_t u) { return type_ok(g, u, type); },
+        [&](uint32_t u) { return any_type(g, u); });
+}
+
+__global__ __launch_bounds__(wide::kBlock) void lookup_wide_select_kernel(Rows g, uint32_t type, wide::State w,
+                                                                          const uint32_t *ovf_list, uint32_t first,
+                                                                          const uint32_t *from, paged::PageOut o) {
+    __shared__ uint32_t s_wave[wide::kBlock / 64];
+    wide::page_select(w, ovf_list, first, from, o, s_wave, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
+__global__ __launch_bounds__(wide::kBlock) void lookup_wide_clear_kernel(Rows g, uint32_t type, wide::State w,
+                                                                         const uint32_t *ovf_list, uint32_t first,
+                                                                         const uint32_t *from) {
+    __shared__ unsigned int s_cnt;
+    wide::page_clear(w, ovf_list, first, from, &s_cnt, [&](uint32_t u) { return type_ok(g, u, type); });
+}
+
 }  // namespace
 
 struct ketogpu_lookup : ListHandle {
@@ -630,16 +657,93 @@ struct ketogpu_lookup : ListHandle {
             },
             [&](uint32_t first, uint32_t k) {
                 wide_round(
-                    first, k, g.N, capacity,
-                    [&](const wide::State &w, unsigned long long lb, unsigned long long le) {
+                    first, k, g.N,
+                    [&](const wide::State &w, uint32_t, unsigned long long lb, unsigned long long le) {
                         KLAUNCH(lookup_wide_level_kernel, dim3(wide::level_grid(le - lb)), dim3(wide::kBlock), 0,
                                 stream, g, type, w, lb, le);
                     },
+                    [&](const wide::State &w) { wide_list_finish(w, first, type, capacity); });
+            });
+    }
+
+    // the wide tier's full-list finish: reserve, then the write kernel
+    void wide_list_finish(const wide::State &w, uint32_t first, uint32_t type, uint64_t capacity) {
+        wide_reserve(w, first, capacity);
+        KLAUNCH(lookup_wide_write_kernel, wide_write_grid(w.nslots), dim3(wide::kBlock), 0, stream, g, type, w,
+                list_out(capacity));
+    }
+
+    uint32_t need_wide_state(uint32_t wanted) {
+        return wst.slots = need_wide_slots(wanted, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+    }
+
+    // a wide round's level launch under the limits d_depth (null: none)
+    void wide_level_depth(const wide::State &w, uint32_t L, unsigned long long lb, unsigned long long le,
+                          uint32_t type, const uint32_t *d_depth, uint32_t first) {
+        KLAUNCH(lookup_wide_level_depth_kernel, dim3(wide::level_grid(le - lb)), dim3(wide::kBlock), 0, stream, g,
+                type, w, lb, le, wide::Cut{L, d_depth, d_ovf.p, first, d_front.p});
+    }
+
+    // ketogpu_lookup_ids_depth_wide: run_depth() with tier 1's overflows in rounds of the wide
+    // tier, counted in wst alone
+    void run_depth_wide(const uint32_t *targets, const uint32_t *max_depth, size_t n, uint32_t type, uint32_t *out,
+                        uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *frontier, uint64_t *needed) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        ListHandle::run_wide(
+            targets, n, out, capacity, begin, count, needed,
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || targets[i] == NONE; },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_depth_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        (uint32_t)n, type, force_tier2 ? 1 : 0, list_out(capacity), d_front.p, d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return need_wide_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                wide_round(
+                    first, k, g.N,
+                    [&](const wide::State &w, uint32_t L, unsigned long long lb, unsigned long long le) {
+                        wide_level_depth(w, L, lb, le, type, d_depth, first);
+                    },
+                    [&](const wide::State &w) { wide_list_finish(w, first, type, capacity); });
+            });
+        read_frontier(frontier, n);
+        wst.last_call_ms = ms_of_call();
+    }
+
+    // ketogpu_lookup_page_wide: run_page_depth() with tier 1's overflows in rounds of the wide
+    // tier and the paged finish of wide.hpp, counted in wst alone
+    void run_page_wide(const uint32_t *targets, const uint32_t *max_depth, const uint32_t *from, size_t n,
+                       uint32_t type, uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count,
+                       uint64_t *remaining, uint64_t *frontier) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        ListHandle::run_page_wide(
+            targets, from, n, limit, out, returned, count, remaining,
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(lookup_depth_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        d_from.p, (uint32_t)n, type, force_tier2 ? 1 : 0, page_out(limit), d_front.p, d_ovf.p,
+                        ovf_count);
+            },
+            [&](uint32_t ovf) { return need_wide_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                wide_round(
+                    first, k, g.N,
+                    [&](const wide::State &w, uint32_t L, unsigned long long lb, unsigned long long le) {
+                        wide_level_depth(w, L, lb, le, type, d_depth, first);
+                    },
                     [&](const wide::State &w) {
-                        KLAUNCH(lookup_wide_write_kernel, wide_write_grid(k), dim3(wide::kBlock), 0, stream, g, type,
-                                w, list_out(capacity));
+                        wide_page_finish(
+                            w, first, limit,
+                            [&](const wide::State &w) {
+                                KLAUNCH(lookup_wide_select_kernel, dim3(k), dim3(wide::kBlock), 0, stream, g, type, w,
+                                        d_ovf.p, first, d_from.p, page_out(limit));
+                            },
+                            [&](const wide::State &w) {
+                                KLAUNCH(lookup_wide_clear_kernel, wide_clear_grid(k), dim3(wide::kBlock), 0, stream, g,
+                                        type, w, d_ovf.p, first, d_from.p);
+                            });
                     });
             });
+        read_frontier(frontier, n);
+        wst.last_call_ms = ms_of_call();
     }
 
     // the paged call: run() with the ordered finish
@@ -849,6 +953,23 @@ int ketogpu_lookup_ids_wide(ketogpu_lookup *l, const uint32_t *targets, size_t n
                             uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *needed) {
     return list_call(l, !needed || (n && (!targets || !begin || !count)) || (capacity && !out), n, "targets", nullptr,
                      [&] { l->run_ids_wide(targets, n, type, out, capacity, begin, count, needed); });
+}
+
+int ketogpu_lookup_ids_depth_wide(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth, size_t n,
+                                  uint32_t type, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                                  uint64_t *frontier, uint64_t *needed) {
+    return list_call(l, !needed || (n && (!targets || !begin || !count)) || (capacity && !out), n, "targets", nullptr,
+                     [&] {
+                         l->run_depth_wide(targets, max_depth, n, type, out, capacity, begin, count, frontier, needed);
+                     });
+}
+
+int ketogpu_lookup_page_wide(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *max_depth,
+                             const uint32_t *from, size_t n, uint32_t type, uint32_t limit, uint32_t *out,
+                             uint32_t *returned, uint64_t *count, uint64_t *remaining, uint64_t *frontier) {
+    return list_call(l, n && (!targets || !out || !returned || !count || !remaining), n, "targets", &limit, [&] {
+        l->run_page_wide(targets, max_depth, from, n, type, limit, out, returned, count, remaining, frontier);
+    });
 }
 
 int ketogpu_lookup_page(ketogpu_lookup *l, const uint32_t *targets, const uint32_t *from, size_t n, uint32_t type,

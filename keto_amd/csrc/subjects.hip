@@ -41,7 +41,10 @@
 // reservations of the closures.
 //
 // The wide call (ketogpu_subjects_ids_wide) is the full-list call with tier 1's overflows run by
-// wide.hpp's level-synchronous tier, spread over the whole device, instead of tier 2.
+// wide.hpp's level-synchronous tier, spread over the whole device, instead of tier 2.  The wide
+// depth and paged calls (ketogpu_subjects_ids_depth_wide / _page_wide) are the depth calls with
+// the same replacement: level L of the wide tier is its launch L, and the paged finish is
+// wide.hpp's select, clear and report.
 //
 // Every index is validated before it is used: roots against N, and against Nx before fwd_off
 // is touched; row entries against N before the class array or a bitmap is.
@@ -577,6 +580,31 @@ __global__ __launch_bounds__(wide::kBlock) void subjects_wide_write_kernel(Rows 
     wide::write(w, o, &s_cnt, &s_at, [&](uint32_t u) { return class_ok(g, u, cls); });
 }
 
+// ketogpu_subjects_ids_depth_wide / _page_wide: the level under a depth limit, and the paged
+// finish's select and clear (wide.hpp "depth", "page")
+__global__ __launch_bounds__(wide::kBlock) void subjects_wide_level_depth_kernel(Rows g, uint32_t cls, wide::State w,
+                                                                                 unsigned long long lb,
+                                                                                 unsigned long long le,
+                                                                                 wide::Cut cut) {
+    wide::level_depth(
+        g, g.N, w, lb, le, cut, [&](uint32_t u) { return class_ok(g, u, cls); },
+        [&](uint32_t u) { return any_class(g, u); });
+}
+
+__global__ __launch_bounds__(wide::kBlock) void subjects_wide_select_kernel(Rows g, uint32_t cls, wide::State w,
+                                                                            const uint32_t *ovf_list, uint32_t first,
+                                                                            const uint32_t *from, paged::PageOut o) {
+    __shared__ uint32_t s_wave[wide::kBlock / 64];
+    wide::page_select(w, ovf_list, first, from, o, s_wave, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
+__global__ __launch_bounds__(wide::kBlock) void subjects_wide_clear_kernel(Rows g, uint32_t cls, wide::State w,
+                                                                           const uint32_t *ovf_list, uint32_t first,
+                                                                           const uint32_t *from) {
+    __shared__ unsigned int s_cnt;
+    wide::page_clear(w, ovf_list, first, from, &s_cnt, [&](uint32_t u) { return class_ok(g, u, cls); });
+}
+
 }  // namespace
 
 struct ketogpu_subjects : ListHandle {
@@ -733,16 +761,93 @@ struct ketogpu_subjects : ListHandle {
             },
             [&](uint32_t first, uint32_t k) {
                 wide_round(
-                    first, k, g.Nx, capacity,
-                    [&](const wide::State &w, unsigned long long lb, unsigned long long le) {
+                    first, k, g.Nx,
+                    [&](const wide::State &w, uint32_t, unsigned long long lb, unsigned long long le) {
                         KLAUNCH(subjects_wide_level_kernel, dim3(wide::level_grid(le - lb)), dim3(wide::kBlock), 0,
                                 stream, g, cls, w, lb, le);
                     },
+                    [&](const wide::State &w) { wide_list_finish(w, first, cls, capacity); });
+            });
+    }
+
+    // the wide tier's full-list finish: reserve, then the write kernel
+    void wide_list_finish(const wide::State &w, uint32_t first, uint32_t cls, uint64_t capacity) {
+        wide_reserve(w, first, capacity);
+        KLAUNCH(subjects_wide_write_kernel, wide_write_grid(w.nslots), dim3(wide::kBlock), 0, stream, g, cls, w,
+                list_out(capacity));
+    }
+
+    uint32_t need_wide_state(uint32_t wanted) {
+        return wst.slots = need_wide_slots(wanted, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+    }
+
+    // a wide round's level launch under the limits d_depth (null: none)
+    void wide_level_depth(const wide::State &w, uint32_t L, unsigned long long lb, unsigned long long le, uint32_t cls,
+                          const uint32_t *d_depth, uint32_t first) {
+        KLAUNCH(subjects_wide_level_depth_kernel, dim3(wide::level_grid(le - lb)), dim3(wide::kBlock), 0, stream, g,
+                cls, w, lb, le, wide::Cut{L, d_depth, d_ovf.p, first, d_front.p});
+    }
+
+    // ketogpu_subjects_ids_depth_wide: run_depth() with tier 1's overflows in rounds of the wide
+    // tier, counted in wst alone
+    void run_depth_wide(const uint32_t *roots, const uint32_t *max_depth, size_t n, uint32_t cls, uint32_t *out,
+                        uint64_t capacity, uint64_t *begin, uint64_t *count, uint64_t *frontier, uint64_t *needed) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        ListHandle::run_wide(
+            roots, n, out, capacity, begin, count, needed,
+            [&](size_t i) { return begin[i] == KETOGPU_LOOKUP_INVALID || roots[i] == NONE; },
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_depth_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        (uint32_t)n, cls, force_tier2 ? 1 : 0, subjects_out(capacity), d_front.p, d_ovf.p, ovf_count);
+            },
+            [&](uint32_t ovf) { return need_wide_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                wide_round(
+                    first, k, g.Nx,
+                    [&](const wide::State &w, uint32_t L, unsigned long long lb, unsigned long long le) {
+                        wide_level_depth(w, L, lb, le, cls, d_depth, first);
+                    },
+                    [&](const wide::State &w) { wide_list_finish(w, first, cls, capacity); });
+            });
+        read_frontier(frontier, n);
+        wst.last_call_ms = ms_of_call();
+    }
+
+    // ketogpu_subjects_page_wide: run_page_depth() with tier 1's overflows in rounds of the wide
+    // tier and the paged finish of wide.hpp, counted in wst alone
+    void run_page_wide(const uint32_t *roots, const uint32_t *max_depth, const uint32_t *from, size_t n, uint32_t cls,
+                       uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count, uint64_t *remaining,
+                       uint64_t *frontier) {
+        const uint32_t *d_depth = upload_depth(max_depth, n);
+        ListHandle::run_page_wide(
+            roots, from, n, limit, out, returned, count, remaining,
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_depth_page_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, g, d_req.p, d_depth,
+                        d_from.p, (uint32_t)n, cls, force_tier2 ? 1 : 0, page_out(limit), d_front.p, d_ovf.p,
+                        ovf_count);
+            },
+            [&](uint32_t ovf) { return need_wide_state(ovf); },
+            [&](uint32_t first, uint32_t k) {
+                wide_round(
+                    first, k, g.Nx,
+                    [&](const wide::State &w, uint32_t L, unsigned long long lb, unsigned long long le) {
+                        wide_level_depth(w, L, lb, le, cls, d_depth, first);
+                    },
                     [&](const wide::State &w) {
-                        KLAUNCH(subjects_wide_write_kernel, wide_write_grid(k), dim3(wide::kBlock), 0, stream, g, cls,
-                                w, list_out(capacity));
+                        wide_page_finish(
+                            w, first, limit,
+                            [&](const wide::State &w) {
+                                KLAUNCH(subjects_wide_select_kernel, dim3(k), dim3(wide::kBlock), 0, stream, g, cls, w,
+                                        d_ovf.p, first, d_from.p, page_out(limit));
+                            },
+                            [&](const wide::State &w) {
+                                KLAUNCH(subjects_wide_clear_kernel, wide_clear_grid(k), dim3(wide::kBlock), 0, stream,
+                                        g, cls, w, d_ovf.p, first, d_from.p);
+                            });
                     });
             });
+        read_frontier(frontier, n);
+        wst.last_call_ms = ms_of_call();
     }
 
     // the paged call: run() with the ordered finish
@@ -1036,6 +1141,24 @@ int ketogpu_subjects_ids_wide(ketogpu_subjects *h, const uint32_t *roots, size_t
     return list_call(h, !needed || (n && (!roots || !begin || !count)) || (capacity && !out), n, "roots", nullptr,
                      [&] { h->run_ids_wide(roots, n, cls, out, capacity, begin, count, needed); });
 }
+
+int ketogpu_subjects_ids_depth_wide(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth, size_t n,
+                                    uint32_t cls, uint32_t *out, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                                    uint64_t *frontier, uint64_t *needed) {
+    return list_call(h, !needed || (n && (!roots || !begin || !count)) || (capacity && !out), n, "roots", nullptr, [&] {
+        h->run_depth_wide(roots, max_depth, n, cls, out, capacity, begin, count, frontier, needed);
+    });
+}
+
+int ketogpu_subjects_page_wide(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *max_depth,
+                               const uint32_t *from, size_t n, uint32_t cls, uint32_t limit, uint32_t *out,
+                               uint32_t *returned, uint64_t *count, uint64_t *remaining, uint64_t *frontier) {
+    return list_call(h, n && (!roots || !out || !returned || !count || !remaining), n, "roots", &limit, [&] {
+        h->run_page_wide(roots, max_depth, from, n, cls, limit, out, returned, count, remaining, frontier);
+    });
+}
+
+uint32_t ketogpu_wide_clear_tile_ids(void) { return wide::kClearTile * 32u; }
 
 int ketogpu_subjects_page(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *from, size_t n, uint32_t cls,
                           uint32_t limit, uint32_t *out, uint32_t *returned, uint64_t *count, uint64_t *remaining) {

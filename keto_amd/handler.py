@@ -15,6 +15,8 @@ caller gets the reference's responses from the new engines:
          the list within that many hops, and the body gains "complete": true | false
          both take via=true (DESIGN.md "Grant trees"; any other value is 400): every entry becomes
          {"object" | "subject": ..., "via": the granting subject, "hops": n}
+         both take wide=true (DESIGN.md "Chip-wide pages and depths"; any other value is 400, and so is
+         wide=true together with via=true): the same body, the large closures run in the wide tier
     GET  /list/objects/combined, /list/subjects/combined  (new, DESIGN.md "Combined listings")  the same bodies for
          the list of two subjects / two objects under op = and | andnot | or
     GET  /check/explain  (new, DESIGN.md "Explain")  200 {"allowed":true,"path":[...]} | 403 {"allowed":false,"path":[]}
@@ -339,6 +341,19 @@ class Handler:
             raise BadRequest(f'via {json.dumps(raw or "")}: expected "true"')
         return True
 
+    @staticmethod
+    def _wide(q, why):
+        """wide -> {} when the parameter is absent, {"wide": True} for "true" (the keyword of the
+        list calls); anything else, and wide=true together with via=true, is a BadRequest"""
+        if "wide" not in q:
+            return {}
+        raw = _get(q, "wide")
+        if raw != "true":
+            raise BadRequest(f'wide {json.dumps(raw or "")}: expected "true"')
+        if why:
+            raise BadRequest("wide=true cannot be combined with via=true")
+        return {"wide": True}
+
     def _list(self, backend, query, call):
         if backend is None:
             return self._error(404, "this server has no list handle")
@@ -356,10 +371,12 @@ class Handler:
     def get_list_objects(self, query):
         """namespace, relation, subject_id | subject_set.*, page_size, page_token -> the objects o
         with Check(namespace:o#relation@subject); with max-depth, those within that many hops
-        of the subject, and "complete"; with via=true every entry is {"object", "via", "hops"} """
+        of the subject, and "complete"; with via=true every entry is {"object", "via", "hops"};
+        wide=true (not with via=true) runs the large closures in the wide tier """
         def call(q, size, token):
             depth = self._max_depth(q)
             why = self._via(q)
+            wide = self._wide(q, why)
             t = tuple_from_url(q)  # the subject is required
             if why:
                 res = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size, token, max_depth=depth,
@@ -371,9 +388,9 @@ class Handler:
                 return body
             if depth is not None:
                 items, nxt, total, complete = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size,
-                                                                            token, max_depth=depth)
+                                                                            token, max_depth=depth, **wide)
                 return {"objects": items, "next_page_token": nxt, "total": total, "complete": bool(complete)}
-            items, nxt, total = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size, token)
+            items, nxt, total = self.lookup.list_objects_page(t.namespace, t.relation, t.subject, size, token, **wide)
             return {"objects": items, "next_page_token": nxt, "total": total}
         return self._list(self.lookup, query, call)
 
@@ -381,10 +398,12 @@ class Handler:
         """namespace, object, relation, kind (ids | any | ns#relation), page_size, page_token -> the
         subjects s with Check(namespace:object#relation@s), in the JSON form check requests use;
         with max-depth, those within that many hops of the object, and "complete"; with via=true
-        every entry is {"subject", "via", "hops"} """
+        every entry is {"subject", "via", "hops"}; wide=true (not with via=true) runs the large
+        closures in the wide tier """
         def call(q, size, token):
             depth = self._max_depth(q)
             why = self._via(q)
+            wide = self._wide(q, why)
             kind = _get(q, "kind") or "ids"
             if kind not in ("ids", "any"):
                 ns, sep, rel = kind.partition("#")
@@ -401,10 +420,10 @@ class Handler:
                 return body
             if depth is not None:
                 items, nxt, total, complete = self.subjects.list_subjects_page(*root, kind, size, token,
-                                                                               max_depth=depth)
+                                                                               max_depth=depth, **wide)
                 return {"subjects": [s.to_dict() for s in items], "next_page_token": nxt, "total": total,
                         "complete": bool(complete)}
-            items, nxt, total = self.subjects.list_subjects_page(*root, kind, size, token)
+            items, nxt, total = self.subjects.list_subjects_page(*root, kind, size, token, **wide)
             return {"subjects": [s.to_dict() for s in items], "next_page_token": nxt, "total": total}
         return self._list(self.subjects, query, call)
 

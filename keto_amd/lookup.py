@@ -37,7 +37,12 @@ distance; `list_*_depth_batch` return names and `complete`, and the named calls 
 
 The full-list calls take a keyword `wide` (ketogpu_*_ids_wide, DESIGN.md "Chip-wide closures"): the
 same lists, with the closures too large for one wave spread over the whole device instead of one
-workgroup each; `wide_stats()` counts them.  The CPU twins accept and ignore it.
+workgroup each; `wide_stats()` counts them.  The CPU twins accept and ignore it.  The paged and the
+depth calls take it too (ketogpu_*_page_wide / ketogpu_*_ids_depth_wide, DESIGN.md "Chip-wide pages
+and depths"): `*_page_raw`, `*_depth_raw`, `*_depth_page_raw`, `list_*_page`, `list_*_page_batch` and
+`list_*_depth_batch`, with or without `max_depth`; together with `with_via` it raises ValueError.
+`list_*_batch` / `ListObjects` / `ListSubjects` keep refusing `wide` with `max_depth`: the depth
+lists by name are `list_*_depth_batch(..., wide=True)`.
 """
 import ctypes as C
 
@@ -120,18 +125,27 @@ def _page_args(ids, from_ids, limit):
     return ids, lo, n, limit, out, returned, count, remaining
 
 
+def _no_wide_via(wide, with_via):
+    """there is no wide via call (DESIGN.md "Chip-wide pages and depths")"""
+    if wide and with_via:
+        raise ValueError("wide=True does not take with_via")
+
+
 class _ObjectPages:
     """list_objects_page over self.lookup_page_raw and self.snapshot"""
 
-    def list_objects_page_batch(self, namespace, relation, requests, page_size=100, max_depth=None, with_via=False):
+    def list_objects_page_batch(self, namespace, relation, requests, page_size=100, max_depth=None, with_via=False,
+                                wide=False):
         """requests: (subject, page_token) pairs, one device call for all of them -> per
         request (object names in node-id order, next_page_token, total).  max_depth (one number,
         or one per request): the objects within that many hops, and a fourth element `complete`.
-        with_via: every item is (name, via, hops), via the subject the granting node stands for"""
+        with_via: every item is (name, via, hops), via the subject the granting node stands for.
+        wide: the large closures run in the wide tier (not with with_via: ValueError)"""
+        _no_wide_via(wide, with_via)
         if with_via:
             return self._list_objects_page_via(namespace, relation, list(requests), page_size, max_depth)
         if max_depth is not None:
-            return self._list_objects_page_depth(namespace, relation, list(requests), page_size, max_depth)
+            return self._list_objects_page_depth(namespace, relation, list(requests), page_size, max_depth, wide)
         page_size = check_page_size(page_size)
         requests = list(requests)
         lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
@@ -139,7 +153,7 @@ class _ObjectPages:
         targets = resolve_subjects(self.snapshot, [s for s, _ in requests])
         if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
             return [([], "", 0) for _ in requests]
-        out, returned, count, remaining = self.lookup_page_raw(targets, lo, ty, page_size)
+        out, returned, count, remaining = self.lookup_page_raw(targets, lo, ty, page_size, wide=wide)
         res = []
         for i in range(len(requests)):
             k = int(returned[i])
@@ -148,13 +162,13 @@ class _ObjectPages:
         return res
 
     def list_objects_page(self, namespace, relation, subject, page_size=100, page_token="", max_depth=None,
-                          with_via=False):
+                          with_via=False, wide=False):
         """-> (items, next_page_token, total): at most page_size object names o with
         Check(namespace:o#relation@subject), in node-id order from the token on.  With max_depth:
         of the objects within that many hops, -> (items, next_page_token, total, complete).  With
-        with_via the items are (name, via, hops)"""
+        with_via the items are (name, via, hops).  wide: as in list_objects_page_batch"""
         return self.list_objects_page_batch(namespace, relation, [(subject, page_token)], page_size, max_depth,
-                                            with_via)[0]
+                                            with_via, wide)[0]
 
     def _list_objects_page_via(self, namespace, relation, requests, page_size, max_depth):
         page_size = check_page_size(page_size)
@@ -175,7 +189,7 @@ class _ObjectPages:
             res.append((items, next_page_token(out[i], k, remaining[i]), int(count[i])) + tail(not frontier[i]))
         return res
 
-    def _list_objects_page_depth(self, namespace, relation, requests, page_size, max_depth):
+    def _list_objects_page_depth(self, namespace, relation, requests, page_size, max_depth, wide=False):
         page_size = check_page_size(page_size)
         lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
         depth = depth_array(max_depth, len(requests))
@@ -183,7 +197,8 @@ class _ObjectPages:
         targets = resolve_subjects(self.snapshot, [s for s, _ in requests])
         if ty == TYPE_NONE:
             return [([], "", 0, True) for _ in requests]
-        out, returned, count, remaining, frontier = self.lookup_depth_page_raw(targets, depth, lo, ty, page_size)
+        out, returned, count, remaining, frontier = self.lookup_depth_page_raw(targets, depth, lo, ty, page_size,
+                                                                               wide=wide)
         res = []
         for i in range(len(requests)):
             k = int(returned[i])
@@ -195,16 +210,19 @@ class _ObjectPages:
 class _SubjectPages:
     """list_subjects_page over self.subject_page_raw and self.snapshot"""
 
-    def list_subjects_page_batch(self, requests, kind="ids", page_size=100, max_depth=None, with_via=False):
+    def list_subjects_page_batch(self, requests, kind="ids", page_size=100, max_depth=None, with_via=False,
+                                 wide=False):
         """requests: ((namespace, object, relation), page_token) pairs, one device call for all
         of them -> per request (SubjectID / SubjectSet in node-id order, next_page_token, total).
         max_depth (one number, or one per request): the subjects within that many hops, and a
         fourth element `complete`.  with_via: every item is (subject, via, hops), via the subject
-        set whose tuple grants it"""
+        set whose tuple grants it.  wide: the large closures run in the wide tier (not with
+        with_via: ValueError)"""
+        _no_wide_via(wide, with_via)
         if with_via:
             return self._list_subjects_page_via(list(requests), kind, page_size, max_depth)
         if max_depth is not None:
-            return self._list_subjects_page_depth(list(requests), kind, page_size, max_depth)
+            return self._list_subjects_page_depth(list(requests), kind, page_size, max_depth, wide)
         page_size = check_page_size(page_size)
         requests = list(requests)
         lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
@@ -212,7 +230,7 @@ class _SubjectPages:
         roots = resolve_roots(self.snapshot, [tuple(r) for r, _ in requests])
         if cls == TYPE_NONE:
             return [([], "", 0) for _ in requests]
-        out, returned, count, remaining = self.subject_page_raw(roots, lo, cls, page_size)
+        out, returned, count, remaining = self.subject_page_raw(roots, lo, cls, page_size, wide=wide)
         res = []
         for i in range(len(requests)):
             k = int(returned[i])
@@ -221,13 +239,13 @@ class _SubjectPages:
         return res
 
     def list_subjects_page(self, namespace, object, relation, kind="ids", page_size=100, page_token="",
-                           max_depth=None, with_via=False):
+                           max_depth=None, with_via=False, wide=False):
         """-> (items, next_page_token, total): at most page_size subjects s with
         Check(namespace:object#relation@s), in node-id order from the token on.  With max_depth:
         of the subjects within that many hops, -> (items, next_page_token, total, complete).  With
-        with_via the items are (subject, via, hops)"""
+        with_via the items are (subject, via, hops).  wide: as in list_subjects_page_batch"""
         return self.list_subjects_page_batch([((namespace, object, relation), page_token)], kind, page_size,
-                                             max_depth, with_via)[0]
+                                             max_depth, with_via, wide)[0]
 
     def _list_subjects_page_via(self, requests, kind, page_size, max_depth):
         page_size = check_page_size(page_size)
@@ -248,7 +266,7 @@ class _SubjectPages:
             res.append((items, next_page_token(out[i], k, remaining[i]), int(count[i])) + tail(not frontier[i]))
         return res
 
-    def _list_subjects_page_depth(self, requests, kind, page_size, max_depth):
+    def _list_subjects_page_depth(self, requests, kind, page_size, max_depth, wide=False):
         page_size = check_page_size(page_size)
         lo = np.array([parse_page_token(tok) for _, tok in requests], dtype=np.uint32)
         depth = depth_array(max_depth, len(requests))
@@ -256,7 +274,8 @@ class _SubjectPages:
         roots = resolve_roots(self.snapshot, [tuple(r) for r, _ in requests])
         if cls == TYPE_NONE:
             return [([], "", 0, True) for _ in requests]
-        out, returned, count, remaining, frontier = self.subject_depth_page_raw(roots, depth, lo, cls, page_size)
+        out, returned, count, remaining, frontier = self.subject_depth_page_raw(roots, depth, lo, cls, page_size,
+                                                                                wide=wide)
         res = []
         for i in range(len(requests)):
             k = int(returned[i])
@@ -352,23 +371,24 @@ class _HostDepth:
 class _ObjectsDepth:
     """the depth-limited object lists over self.lookup_depth_raw and self.snapshot"""
 
-    def lookup_depth(self, targets, max_depth, type_id=TYPE_ANY, capacity=None):
+    def lookup_depth(self, targets, max_depth, type_id=TYPE_ANY, capacity=None, wide=False):
         """-> (one ascending uint32 array per target, frontier): lookup_ids within max_depth hops
         (one number, or one per target; DEPTH_ALL: no limit), with lookup_ids' re-issue of
-        truncated lists.  frontier[i] == 0: list i is the whole closure."""
-        return _depth_lists(lambda t, d, c: self.lookup_depth_raw(t, d, type_id, c), targets, max_depth, capacity,
-                            None)
+        truncated lists.  frontier[i] == 0: list i is the whole closure.  wide: the large closures
+        run in the wide tier."""
+        return _depth_lists(lambda t, d, c: self.lookup_depth_raw(t, d, type_id, c, wide=wide), targets, max_depth,
+                            capacity, None)
 
-    def list_objects_depth_batch(self, namespace, relation, subjects, max_depth):
+    def list_objects_depth_batch(self, namespace, relation, subjects, max_depth, wide=False):
         """per subject: the sorted object names o with Check(namespace:o#relation@subject) that
         are within max_depth hops of the subject -> (lists, complete); complete[i]: no deeper
-        level was cut off, list i is what list_objects_batch gives"""
+        level was cut off, list i is what list_objects_batch gives.  wide: as in lookup_depth"""
         ty = self.snapshot.type_id(namespace, relation)
         targets = resolve_subjects(self.snapshot, list(subjects))
         depth = depth_array(max_depth, len(targets))
         if ty == TYPE_NONE:  # unknown namespace or unused pair: nothing (check answers false there)
             return [[] for _ in targets], [True] * len(targets)
-        lists, frontier = self.lookup_depth(targets, depth, ty)
+        lists, frontier = self.lookup_depth(targets, depth, ty, wide=wide)
         return ([sorted(self.snapshot.node_info(int(v))["id"] for v in ids) for ids in lists],
                 [not f for f in frontier])
 
@@ -376,22 +396,25 @@ class _ObjectsDepth:
 class _SubjectsDepth:
     """the depth-limited subject lists over self.subject_depth_raw and self.snapshot"""
 
-    def subject_depth(self, roots, max_depth, cls=TYPE_ANY, capacity=None):
+    def subject_depth(self, roots, max_depth, cls=TYPE_ANY, capacity=None, wide=False):
         """-> (one ascending uint32 array per root, frontier): subject_ids within max_depth hops
         (one number, or one per root; DEPTH_ALL: no limit), with subject_ids' re-issue of
-        truncated lists.  frontier[i] == 0: list i is the whole closure."""
-        return _depth_lists(lambda r, d, c: self.subject_depth_raw(r, d, cls, c), roots, max_depth, capacity, None)
+        truncated lists.  frontier[i] == 0: list i is the whole closure.  wide: the large closures
+        run in the wide tier."""
+        return _depth_lists(lambda r, d, c: self.subject_depth_raw(r, d, cls, c, wide=wide), roots, max_depth,
+                            capacity, None)
 
-    def list_subjects_depth_batch(self, roots, max_depth, kind="ids"):
+    def list_subjects_depth_batch(self, roots, max_depth, kind="ids", wide=False):
         """per (namespace, object, relation) root: the subjects s with Check(root@s) that are
-        within max_depth hops of the root -> (lists, complete), as list_subjects_batch lists them"""
+        within max_depth hops of the root -> (lists, complete), as list_subjects_batch lists them.
+        wide: as in subject_depth"""
         roots = list(roots)
         cls = _class_of_kind(self.snapshot, kind)
         ids = resolve_roots(self.snapshot, roots)
         depth = depth_array(max_depth, len(ids))
         if cls == TYPE_NONE:
             return [[] for _ in roots], [True] * len(roots)
-        lists, frontier = self.subject_depth(ids, depth, cls)
+        lists, frontier = self.subject_depth(ids, depth, cls, wide=wide)
         return [_subjects_of(self.snapshot, v) for v in lists], [not f for f in frontier]
 
 
@@ -867,10 +890,13 @@ class _Handle:
                                 count.ctypes.data, C.byref(needed)))
         return out[:int(capacity)], begin[:n], count[:n], needed.value
 
-    def _page_raw(self, requests, from_ids, filter_id, limit):
+    def _page_raw(self, requests, from_ids, filter_id, limit, wide=False):
         """one ketogpu_<ABI>_page call -> (out[n, limit], returned, count, remaining): row i
         holds the returned[i] smallest members >= from_ids[i], ascending; count[i] the whole
-        list's size; returned[i] PAGE_INVALID for an id outside the snapshot"""
+        list's size; returned[i] PAGE_INVALID for an id outside the snapshot.  wide: one
+        ketogpu_<ABI>_page_wide call without a depth limit, the same results"""
+        if wide:
+            return self._page_depth_raw(requests, None, from_ids, filter_id, limit, wide=True)[:4]
         requests, lo, n, limit, out, returned, count, remaining = _page_args(requests, from_ids, limit)
         L.check(self._abi("page")(self.h, requests.ctypes.data, None if lo is None else lo.ctypes.data, n,
                                   int(filter_id), limit, out.ctypes.data, returned.ctypes.data, count.ctypes.data,
@@ -881,10 +907,11 @@ class _Handle:
     def depth_stats(self):
         return self._stats(L.DepthStats(), "depth_stats_get")
 
-    def _ids_depth_raw(self, requests, max_depth, filter_id=TYPE_ANY, capacity=0):
+    def _ids_depth_raw(self, requests, max_depth, filter_id=TYPE_ANY, capacity=0, wide=False):
         """one ketogpu_<ABI>_ids_depth call -> (out, begin, count, frontier, needed): _ids_raw's
         results within max_depth hops (None: no limit; one number for all requests, or one per
-        request), and frontier[i], the interior members at exactly that distance"""
+        request), and frontier[i], the interior members at exactly that distance.  wide: one
+        ketogpu_<ABI>_ids_depth_wide call, the same results"""
         requests = np.ascontiguousarray(requests, dtype=np.uint32)
         n = len(requests)
         depth = depth_array(max_depth, n)
@@ -893,21 +920,23 @@ class _Handle:
         count = np.empty(max(n, 1), dtype=np.uint64)
         frontier = np.zeros(max(n, 1), dtype=np.uint64)
         needed = C.c_uint64()
-        L.check(self._abi("ids_depth")(self.h, requests.ctypes.data, None if depth is None else depth.ctypes.data, n,
-                                       int(filter_id), out.ctypes.data if capacity else None, int(capacity),
-                                       begin.ctypes.data, count.ctypes.data, frontier.ctypes.data, C.byref(needed)))
+        call = self._abi("ids_depth_wide" if wide else "ids_depth")
+        L.check(call(self.h, requests.ctypes.data, None if depth is None else depth.ctypes.data, n, int(filter_id),
+                     out.ctypes.data if capacity else None, int(capacity), begin.ctypes.data, count.ctypes.data,
+                     frontier.ctypes.data, C.byref(needed)))
         return out[:int(capacity)], begin[:n], count[:n], frontier[:n], needed.value
 
-    def _page_depth_raw(self, requests, max_depth, from_ids=None, filter_id=TYPE_ANY, limit=100):
+    def _page_depth_raw(self, requests, max_depth, from_ids=None, filter_id=TYPE_ANY, limit=100, wide=False):
         """one ketogpu_<ABI>_page_depth call -> (out[n, limit], returned, count, remaining,
-        frontier): _page_raw's results within max_depth hops"""
+        frontier): _page_raw's results within max_depth hops.  wide: one ketogpu_<ABI>_page_wide
+        call, the same results"""
         requests, lo, n, limit, out, returned, count, remaining = _page_args(requests, from_ids, limit)
         depth = depth_array(max_depth, n)
         frontier = np.zeros(max(n, 1), dtype=np.uint64)
-        L.check(self._abi("page_depth")(self.h, requests.ctypes.data, None if depth is None else depth.ctypes.data,
-                                        None if lo is None else lo.ctypes.data, n, int(filter_id), limit,
-                                        out.ctypes.data, returned.ctypes.data, count.ctypes.data,
-                                        remaining.ctypes.data, frontier.ctypes.data))
+        call = self._abi("page_wide" if wide else "page_depth")
+        L.check(call(self.h, requests.ctypes.data, None if depth is None else depth.ctypes.data,
+                     None if lo is None else lo.ctypes.data, n, int(filter_id), limit, out.ctypes.data,
+                     returned.ctypes.data, count.ctypes.data, remaining.ctypes.data, frontier.ctypes.data))
         return out[:n], returned[:n], count[:n], remaining[:n], frontier[:n]
 
     # ---- listings that say why
@@ -1059,13 +1088,13 @@ class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth, _Ob
         """one ketogpu_lookup_page_via call (_page_via_raw)"""
         return self._page_via_raw(targets, max_depth, from_ids, type_id, limit)
 
-    def lookup_depth_raw(self, targets, max_depth, type_id=TYPE_ANY, capacity=0):
-        """one ketogpu_lookup_ids_depth call (_ids_depth_raw)"""
-        return self._ids_depth_raw(targets, max_depth, type_id, capacity)
+    def lookup_depth_raw(self, targets, max_depth, type_id=TYPE_ANY, capacity=0, wide=False):
+        """one ketogpu_lookup_ids_depth call (_ids_depth_raw); wide: ketogpu_lookup_ids_depth_wide"""
+        return self._ids_depth_raw(targets, max_depth, type_id, capacity, wide=wide)
 
-    def lookup_depth_page_raw(self, targets, max_depth, from_ids=None, type_id=TYPE_ANY, limit=100):
-        """one ketogpu_lookup_page_depth call (_page_depth_raw)"""
-        return self._page_depth_raw(targets, max_depth, from_ids, type_id, limit)
+    def lookup_depth_page_raw(self, targets, max_depth, from_ids=None, type_id=TYPE_ANY, limit=100, wide=False):
+        """one ketogpu_lookup_page_depth call (_page_depth_raw); wide: ketogpu_lookup_page_wide"""
+        return self._page_depth_raw(targets, max_depth, from_ids, type_id, limit, wide=wide)
 
     def lookup_ids_raw(self, targets, type_id=TYPE_ANY, capacity=0, wide=False):
         """one ketogpu_lookup_ids call (_ids_raw); wide: one ketogpu_lookup_ids_wide call, the
@@ -1086,9 +1115,9 @@ class Lookup(_Handle, _ObjectPages, _Paths, _ObjectsCombined, _ObjectsDepth, _Ob
             raise L.KetoError(L.EINVAL, "one target per root")
         return self._ids_raw("paths", [roots, targets], [], capacity)
 
-    def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100):
-        """one ketogpu_lookup_page call (_page_raw)"""
-        return self._page_raw(targets, from_ids, type_id, limit)
+    def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100, wide=False):
+        """one ketogpu_lookup_page call (_page_raw); wide: ketogpu_lookup_page_wide without a limit"""
+        return self._page_raw(targets, from_ids, type_id, limit, wide=wide)
 
 
 def host_list_objects(snapshot, namespace, relation, subject):
@@ -1127,10 +1156,10 @@ class HostLookup(_ObjectPages, _Paths, _HostCombine, _ObjectsCombined, _HostDept
             return np.zeros(0, dtype=np.uint32), 0
         return host_lookup_depth(self.snapshot, x, k, type_id)
 
-    def lookup_depth_raw(self, targets, max_depth, type_id=TYPE_ANY, capacity=0):
+    def lookup_depth_raw(self, targets, max_depth, type_id=TYPE_ANY, capacity=0, wide=False):
         return self._ids_depth_raw(targets, max_depth, type_id, capacity)
 
-    def lookup_depth_page_raw(self, targets, max_depth, from_ids=None, type_id=TYPE_ANY, limit=100):
+    def lookup_depth_page_raw(self, targets, max_depth, from_ids=None, type_id=TYPE_ANY, limit=100, wide=False):
         return self._page_depth_raw(targets, max_depth, from_ids, type_id, limit)
 
     def _members(self, x, type_id):
@@ -1162,7 +1191,7 @@ class HostLookup(_ObjectPages, _Paths, _HostCombine, _ObjectsCombined, _HostDept
             cursor += len(ids)  # every path reserves, written or not
         return out, begin, count, cursor
 
-    def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100):
+    def lookup_page_raw(self, targets, from_ids=None, type_id=TYPE_ANY, limit=100, wide=False):
         targets = np.ascontiguousarray(targets, dtype=np.uint32)
         n_nodes = self.snapshot.stats()["num_nodes"]
         invalid = [t >= n_nodes and t != L.NODE_NONE for t in targets]
@@ -1228,13 +1257,13 @@ class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth, _Subje
         """one ketogpu_subjects_page_via call (_page_via_raw)"""
         return self._page_via_raw(roots, max_depth, from_ids, cls, limit)
 
-    def subject_depth_raw(self, roots, max_depth, cls=TYPE_ANY, capacity=0):
-        """one ketogpu_subjects_ids_depth call (_ids_depth_raw)"""
-        return self._ids_depth_raw(roots, max_depth, cls, capacity)
+    def subject_depth_raw(self, roots, max_depth, cls=TYPE_ANY, capacity=0, wide=False):
+        """one ketogpu_subjects_ids_depth call (_ids_depth_raw); wide: ketogpu_subjects_ids_depth_wide"""
+        return self._ids_depth_raw(roots, max_depth, cls, capacity, wide=wide)
 
-    def subject_depth_page_raw(self, roots, max_depth, from_ids=None, cls=TYPE_ANY, limit=100):
-        """one ketogpu_subjects_page_depth call (_page_depth_raw)"""
-        return self._page_depth_raw(roots, max_depth, from_ids, cls, limit)
+    def subject_depth_page_raw(self, roots, max_depth, from_ids=None, cls=TYPE_ANY, limit=100, wide=False):
+        """one ketogpu_subjects_page_depth call (_page_depth_raw); wide: ketogpu_subjects_page_wide"""
+        return self._page_depth_raw(roots, max_depth, from_ids, cls, limit, wide=wide)
 
     def subject_ids_raw(self, roots, cls=TYPE_ANY, capacity=0, wide=False):
         """one ketogpu_subjects_ids call (_ids_raw); wide: one ketogpu_subjects_ids_wide call, the
@@ -1244,9 +1273,9 @@ class Subjects(_Handle, _SubjectPages, _SubjectsCombined, _SubjectsDepth, _Subje
     def wide_stats(self):
         return self._stats(L.WideStats(), "wide_stats_get")
 
-    def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100):
-        """one ketogpu_subjects_page call (_page_raw)"""
-        return self._page_raw(roots, from_ids, cls, limit)
+    def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100, wide=False):
+        """one ketogpu_subjects_page call (_page_raw); wide: ketogpu_subjects_page_wide without a limit"""
+        return self._page_raw(roots, from_ids, cls, limit, wide=wide)
 
 
 class HostSubjects(_SubjectPages, _HostCombine, _SubjectsCombined, _HostDepth, _SubjectsDepth, _HostVia,
@@ -1275,16 +1304,16 @@ class HostSubjects(_SubjectPages, _HostCombine, _SubjectsCombined, _HostDepth, _
             return np.zeros(0, dtype=np.uint32), 0
         return host_subjects_depth(self.snapshot, x, k, cls)
 
-    def subject_depth_raw(self, roots, max_depth, cls=TYPE_ANY, capacity=0):
+    def subject_depth_raw(self, roots, max_depth, cls=TYPE_ANY, capacity=0, wide=False):
         return self._ids_depth_raw(roots, max_depth, cls, capacity)
 
-    def subject_depth_page_raw(self, roots, max_depth, from_ids=None, cls=TYPE_ANY, limit=100):
+    def subject_depth_page_raw(self, roots, max_depth, from_ids=None, cls=TYPE_ANY, limit=100, wide=False):
         return self._page_depth_raw(roots, max_depth, from_ids, cls, limit)
 
     def _members(self, x, cls):
         return self._side(x, cls, host_subjects)
 
-    def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100):
+    def subject_page_raw(self, roots, from_ids=None, cls=TYPE_ANY, limit=100, wide=False):
         roots = np.ascontiguousarray(roots, dtype=np.uint32)
         n_nodes = self.snapshot.stats()["num_nodes"]
         invalid = [r >= n_nodes and r != L.NODE_NONE for r in roots]
