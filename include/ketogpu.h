@@ -1588,6 +1588,63 @@ int ketogpu_lookup_page_wide(ketogpu_lookup *l, const uint32_t *targets, const u
 /* ids one workgroup of the paged finish's clear kernel covers */
 uint32_t ketogpu_wide_clear_tile_ids(void);
 
+/* ------------------------------------------------------- chip-wide BuildTree */
+/* ketogpu_subjects_expand with the copying spread over the device (DESIGN.md "Chip-wide
+ * BuildTree").  The arguments and the output contract are those of ketogpu_subjects_expand word
+ * for word: count[i] the exact tree size; begin[i] the tree's offset in both output arrays, or
+ * KETOGPU_LOOKUP_TRUNCATED (nothing of the tree was written) or KETOGPU_LOOKUP_INVALID; *needed
+ * the sum of the counts; capacity 0 with NULL outputs only counts; status[i] KETOGPU_EXPAND_OK /
+ * _NIL / _HOST under the same rules, HOST for every request of a snapshot with shared
+ * Subject.String() keys; the same following of in-place writes.  Every OK tree equals the host
+ * twin's, and the plain call's, word for word.
+ *
+ * The walk stays ordered, one wave per request, but it looks only at the row entries that can
+ * do more than emit a leaf: those that have a row of their own or whose bit is set in the bad-row
+ * bitmap.  A bitmap with one bit per word of the handle's rows (free words of the arena included;
+ * mask_words 64-bit words) marks them.  It is rebuilt in full, by one kernel across the device,
+ * by the first wide call after the rows changed (upload, patched or full refresh); a call behind
+ * which nothing changed builds nothing.  In front of each 64-entry step the walk reads up to 64
+ * mask words: at least 64 entries without a mark, or all that is left of the row, are a RUN,
+ * passed in one step of up to 4096 entries with no access to the visited set.  The writing walk
+ * copies a short run itself and appends a longer one to the call's queue as items of up to
+ * `chunk` entries (source, destination, length); a fill kernel launched behind the walk, with no
+ * host wait in between, copies the items with the whole device.  The queue holds queue_capacity
+ * items (KETOGPU_EXPAND_WIDE_QUEUE; the default, 65536 items of 24 bytes, is about ten times
+ * what 1024 trees of 16.4 M nodes append); a run that finds it full is copied by its wave
+ * (runs_queue_full): slower, never an error.  A count-only call, a truncated tree and a HOST
+ * request queue nothing.  A request that opens more than set_capacity nodes runs tier 2 of
+ * ketogpu_subjects_expand unchanged, so KETOGPU_SUBJECTS_TIER=2 makes this call the plain one.
+ * Wide expand calls count only here: neither ketogpu_expand_stats nor any listing statistic
+ * moves, and no plain call is routed here.
+ * (Additions within ABI 9: no existing entry point or struct layout changed.) */
+typedef struct {
+    uint64_t requests;       /* as in ketogpu_expand_stats, for wide expand calls ...       */
+    uint64_t tier1_requests;
+    uint64_t tier2_requests;
+    uint64_t tier2_rounds;
+    uint64_t host_requests;
+    uint64_t nodes_produced;
+    uint64_t truncated_trees;
+    uint64_t mask_builds;      /* full rebuilds of the attention bitmap                     */
+    uint64_t mask_words;       /* its 64-bit words as last built: 8 bytes each on the device */
+    uint64_t run_steps;        /* run steps of all walks, counting and writing              */
+    uint64_t skipped_entries;  /* row entries those steps passed                            */
+    uint64_t runs_queued;      /* runs of writing walks that went to the queue ...          */
+    uint64_t items_queued;     /* ... as this many items                                    */
+    uint64_t runs_self_copied; /* runs of writing walks copied by the walking wave: short
+                                  ones, and those that met a full queue                     */
+    uint64_t runs_queue_full;  /* ... the latter alone                                      */
+    uint64_t queue_capacity;   /* items                                                     */
+    uint32_t slots;            /* tier 2: requests per round (0 before the first)           */
+    uint32_t chunk;            /* row entries per item at most                              */
+    double last_call_ms;       /* host wall time of the last wide expand call               */
+    double last_mask_ms;       /* ... and of the last rebuild of the bitmap, kernel and wait */
+} ketogpu_expand_wide_stats;
+int ketogpu_subjects_expand_wide_stats_get(const ketogpu_subjects *h, ketogpu_expand_wide_stats *out);
+int ketogpu_subjects_expand_wide(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *rest_depth, size_t n,
+                                 uint32_t *out_nodes, uint32_t *out_children, uint64_t capacity, uint64_t *begin,
+                                 uint64_t *count, uint32_t *status, uint64_t *needed);
+
 /* ------------------------------------------------------------------- misc */
 const char *ketogpu_last_error(void);
 int ketogpu_abi_version(void);

@@ -412,6 +412,18 @@ class ExpandStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# include/ketogpu.h chip-wide BuildTree
+class ExpandWideStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "requests", "tier1_requests", "tier2_requests", "tier2_rounds", "host_requests", "nodes_produced",
+        "truncated_trees", "mask_builds", "mask_words", "run_steps", "skipped_entries", "runs_queued",
+        "items_queued", "runs_self_copied", "runs_queue_full", "queue_capacity")] + [
+        ("slots", C.c_uint32), ("chunk", C.c_uint32), ("last_call_ms", C.c_double), ("last_mask_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # include/ketogpu.h chip-wide closures
 class WideStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
@@ -603,6 +615,9 @@ SIGNATURES = {
     "ketogpu_tree_from_ids": (C.c_int, [vp, vp, vp, C.c_uint64, C.POINTER(vp)]),
     "ketogpu_subjects_expand_stats_get": (C.c_int, [vp, C.POINTER(ExpandStats)]),
     "ketogpu_subjects_expand": (C.c_int, [vp, vp, vp, sz, vp, vp, C.c_uint64, vp, vp, vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_subjects_expand_wide_stats_get": (C.c_int, [vp, C.POINTER(ExpandWideStats)]),
+    "ketogpu_subjects_expand_wide": (C.c_int, [vp, vp, vp, sz, vp, vp, C.c_uint64, vp, vp, vp,
+                                               C.POINTER(C.c_uint64)]),
     "ketogpu_subjects_wide_stats_get": (C.c_int, [vp, C.POINTER(WideStats)]),
     "ketogpu_lookup_wide_stats_get": (C.c_int, [vp, C.POINTER(WideStats)]),
     "ketogpu_subjects_ids_wide": (C.c_int, [vp, vp, sz, u32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]),

@@ -15,7 +15,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("KETOGPU_ARCH", "gfx950")
 
 SOURCES = ["snapshot.cpp", "snapshot_write.cpp", "snapshot_io.cpp", "host_engine.cpp", "multi_engine.cpp", "shard.cpp", "device_engine.hip", "partition.hip", "comm.cpp", "part_round.cpp", "tier.cpp", "core_index.cpp", "labels.cpp", "probe.hip", "packed24.cpp", "lookup_host.cpp", "lookup.hip", "subjects_host.cpp", "subjects.hip"]
-HEADERS = ["ketogpu_internal.hpp", "device_util.hpp", "part_round.hpp", "tier.hpp", "core_index.hpp", "labels.hpp", "lookup.hpp", "hip_host.hpp", "subjects.hpp", "paged_finish.hpp", "closure.hpp", "combine.hpp", "depth.hpp", "via.hpp", "expand_tree.hpp", "wide.hpp", os.path.join("..", "..", "include", "ketogpu.h")]
+HEADERS = ["ketogpu_internal.hpp", "device_util.hpp", "part_round.hpp", "tier.hpp", "core_index.hpp", "labels.hpp", "lookup.hpp", "hip_host.hpp", "subjects.hpp", "paged_finish.hpp", "closure.hpp", "combine.hpp", "depth.hpp", "via.hpp", "expand_tree.hpp", "expand_wide.hpp", "wide.hpp", os.path.join("..", "..", "include", "ketogpu.h")]
 
 
 def kernel_source_hash():

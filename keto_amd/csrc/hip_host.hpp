@@ -147,6 +147,7 @@ struct ListHandle {
     std::mutex mu;  // one call at a time per handle
     std::chrono::steady_clock::time_point t0;  // when the call at hand began
     uint64_t version = ~0ull;
+    uint64_t rows_epoch = 0;  // moves whenever the rows, their bounds or N / Nx changed on the device
     closure::Rows g{};      // the rows and per-node labels of the snapshot's current version
     DBuf<uint64_t> d_off;
     DBuf<uint32_t> d_col, d_label;
@@ -254,7 +255,7 @@ struct ListHandle {
         if (moved) drop_tier2();
         g = closure::Rows{d_off.p, d_col.p, d_label.p, s.N, s.Nx, s.Ni, end ? d_end.p : nullptr};
         bound = new_bound, bm_words = ((uint64_t)bound + 31) / 32;
-        version = s.version;
+        version = s.version, rows_epoch++;
         n_rows = n_off - 1, col_words = col_room, key_words = label_room;
         full_bytes = (uint64_t)n_off * 8 * (end ? 2 : 1) + (uint64_t)n_col * 4 + (uint64_t)n_label * 4;
         rst.full_uploads++;
@@ -371,7 +372,7 @@ struct ListHandle {
         }
         patch_pos = s.patch_end();
         s.reader_at(this, patch_pos);
-        version = s.version;
+        version = s.version, rows_epoch++;
         rst.patched_refreshes++;
         rst.rows_patched += patch_nodes.size();
         rst.rows_moved += moves.size();

@@ -53,6 +53,7 @@
 #include "combine.hpp"
 #include "depth.hpp"
 #include "expand_tree.hpp"
+#include "expand_wide.hpp"
 #include "hip_host.hpp"
 #include "subjects.hpp"
 #include "via.hpp"
@@ -563,6 +564,33 @@ __global__ __launch_bounds__(kT2Block) void subjects_expand_tier2_kernel(expand:
     expand::tier2_tree(x, roots[i], depths[i], i, sl, s, &s_base, o);
 }
 
+// ketogpu_subjects_expand_wide: the bodies are expand_wide.hpp's.  The mask kernel runs when the
+// rows changed, the fill kernel in-stream behind tier 1; tier 2 is the kernel above.
+__global__ __launch_bounds__(expand::xwide::kMaskBlock) void subjects_expand_mask_kernel(expand::Graph x,
+                                                                                        uint64_t col_words,
+                                                                                        unsigned long long *mask,
+                                                                                        uint64_t words) {
+    expand::xwide::mask_build(x, col_words, mask, words);
+}
+
+__global__ __launch_bounds__(64) void subjects_expand_wide_tier1_kernel(expand::Graph x,
+                                                                        const unsigned long long *mask,
+                                                                        expand::xwide::Queue q, const uint32_t *roots,
+                                                                        const uint32_t *depths, uint32_t n,
+                                                                        int force_tier2, expand::TreeOut o,
+                                                                        uint32_t *ovf_list, unsigned int *ovf_count) {
+    __shared__ expand::T1Lds s;
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    expand::xwide::tier1_tree(x, mask, q, roots, depths, i, lane, force_tier2, o, ovf_list, ovf_count, s);
+}
+
+__global__ __launch_bounds__(expand::xwide::kFillBlock) void subjects_expand_fill_kernel(expand::Graph x,
+                                                                                        expand::xwide::Queue q,
+                                                                                        expand::TreeOut o) {
+    expand::xwide::fill(x, q, o);
+}
+
 // ---------------------------------------------------------------------- the wide tier
 // ketogpu_subjects_ids_wide: the bodies are wide.hpp's, over the forward rows: the ids below Nx
 // have a row, the member bound is N.  The slot's bitmap is tier 2's; seen lists and worklists
@@ -624,9 +652,16 @@ struct ketogpu_subjects : ListHandle {
     DBuf<uint32_t> d_bad;
     bool has_bad = false;
     uint32_t bad_n = 0;  // the nodes the mirror covers
+    // wide expand calls (expand_wide.hpp): the attention mask over d_col, as of rows_epoch
+    // mask_epoch; the call's queue of copy items and its counters
+    ketogpu_expand_wide_stats xwst{};
+    DBuf<unsigned long long> d_xmask, d_xwctr;
+    DBuf<expand::xwide::Item> d_xwq;
+    uint64_t mask_epoch = ~0ull;
+    uint64_t xwq_cap = expand::xwide::kQueueDefault;
 
     ketogpu_subjects() : ListHandle("subject listing") {}
-    ~ketogpu_subjects() { d_bad.drop(); }
+    ~ketogpu_subjects() { d_bad.drop(), d_xmask.drop(), d_xwctr.drop(), d_xwq.drop(); }
 
     void push_bad() {
         has_bad = std::any_of(h_bad.begin(), h_bad.end(), [](uint32_t w) { return w != 0; });
@@ -1027,7 +1062,8 @@ struct ketogpu_subjects : ListHandle {
     }
 
     // ... then the visited map is not keyed by node: every request is the host's
-    void expand_all_host(size_t n, uint64_t *begin, uint64_t *count, uint32_t *status, uint64_t *needed) {
+    template <class Stats>
+    void expand_all_host(Stats &xst, size_t n, uint64_t *begin, uint64_t *count, uint32_t *status, uint64_t *needed) {
         *needed = 0;
         for (size_t i = 0; i < n; i++) begin[i] = 0, count[i] = 0, status[i] = KETOGPU_EXPAND_HOST;
         xst.requests += n, xst.host_requests += n;
@@ -1084,6 +1120,94 @@ struct ketogpu_subjects : ListHandle {
         xst.last_call_ms = ms_of_call();
     }
 
+    // the attention mask of the rows as they are now (expand_wide.hpp "mask"): rebuilt in full
+    // when an upload or a patched refresh has moved rows_epoch, which covers col, off / end,
+    // N / Nx and the bad-row bitmap; a call behind which nothing changed builds nothing.  A full
+    // rebuild is one pass over col: patching the mask would have to find every occurrence of a
+    // node whose row became empty or non-empty, which is a pass over col too
+    const unsigned long long *need_expand_mask(const expand::Graph &x) {
+        if (mask_epoch == rows_epoch && d_xmask.p) return d_xmask.p;
+        const uint64_t words = (col_words + 63) / 64;
+        d_xmask.need(words);
+        HIP_CHECK(hipStreamSynchronize(stream));  // (the refresh's copies and patch kernel: not the mask's time)
+        const auto m0 = std::chrono::steady_clock::now();
+        if (words) {
+            const uint64_t groups = (words + expand::xwide::kMaskBlock / 64 - 1) / (expand::xwide::kMaskBlock / 64);
+            KLAUNCH(subjects_expand_mask_kernel, dim3((unsigned)std::min<uint64_t>(groups, expand::xwide::kMaskGridMax)),
+                    dim3(expand::xwide::kMaskBlock), 0, stream, x, col_words, d_xmask.p, words);
+            HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        xwst.last_mask_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - m0).count();
+        xwst.mask_builds++, xwst.mask_words = words;
+        mask_epoch = rows_epoch;
+        return d_xmask.p;
+    }
+
+    // ketogpu_subjects_expand_wide: run_expand() with the wide walk in tier 1's place and the
+    // fill kernel right behind it, counted in xwst alone
+    void run_expand_wide(const uint32_t *roots, const uint32_t *depths, size_t n, uint32_t *out_nodes,
+                         uint32_t *out_children, uint64_t capacity, uint64_t *begin, uint64_t *count,
+                         uint32_t *status, uint64_t *needed) {
+        namespace xw = expand::xwide;
+        Tally t{};
+        *needed = 0;
+        xwst.requests += n;
+        if (!n) return;
+        d_req.need(n), d_req2.need(n), d_ovf.need(n), d_begin.need(n), d_count.need(n), d_ret.need(n);
+        d_ctr.need(kCtrs), d_out.need(capacity), d_via.need(capacity);
+        d_xwq.need(xwq_cap), d_xwctr.need(xw::kCtrWords);
+        const expand::Graph x{g, has_bad ? d_bad.p : nullptr};
+        const unsigned long long *mask = need_expand_mask(x);
+        HIP_CHECK(hipMemcpyAsync(d_req.p, roots, n * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(d_req2.p, depths, n * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemsetAsync(d_xwctr.p, 0, xw::kCtrWords * 8, stream));
+        const expand::TreeOut o{list_out(capacity), d_via.p, d_ret.p};
+        const xw::Queue q{d_xwq.p, xwq_cap, d_xwctr.p};
+        run_tiers(
+            xwst, t,
+            [&](unsigned int *ovf_count) {
+                KLAUNCH(subjects_expand_wide_tier1_kernel, dim3((unsigned)n), dim3(64), 0, stream, x, mask, q, d_req.p,
+                        d_req2.p, (uint32_t)n, force_tier2 ? 1 : 0, o, d_ovf.p, ovf_count);
+                if (capacity && !force_tier2)  // (a count-only call queues nothing)
+                    KLAUNCH(subjects_expand_fill_kernel, dim3(xw::kFillGrid), dim3(xw::kFillBlock), 0, stream, x, q, o);
+            },
+            [&](uint32_t ovf) {
+                return xwst.slots = need_expand_slots(ovf, slot_words(), [&](uint32_t k) { return alloc_slots(k); });
+            },
+            [&](uint32_t first, uint32_t k) {
+                KLAUNCH(subjects_expand_tier2_kernel, dim3(k), dim3(kT2Block), 0, stream, x, d_req.p, d_req2.p, o,
+                        d_ovf.p, first, d_bm.p, bm_words, d_aux.p, list_cap, d_xstack.p, expand_stack_words);
+            },
+            [&](Tally &t) { read_ctrs(t); });  // (the cursor has moved)
+        unsigned long long c[xw::kCtrWords];
+        HIP_CHECK(hipMemcpyAsync(begin, d_begin.p, n * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(count, d_count.p, n * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(status, d_ret.p, n * 4, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(c, d_xwctr.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        // (the written trees tile a prefix of both arrays: no word outside a written tree is touched)
+        const uint64_t written = std::min<uint64_t>(written_end(begin, count, n), capacity);
+        if (written && out_nodes) {
+            HIP_CHECK(hipMemcpyAsync(out_nodes, d_out.p, written * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(out_children, d_via.p, written * 4, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        *needed = t.ctr[0];
+        uint64_t unlisted = 0;
+        for (size_t i = 0; i < n; i++) {
+            unlisted += begin[i] == KETOGPU_LOOKUP_INVALID || roots[i] == NONE;
+            xwst.host_requests += status[i] == KETOGPU_EXPAND_HOST;
+        }
+        xwst.tier2_requests += t.ovf;
+        xwst.tier1_requests += n - t.ovf - unlisted;
+        xwst.nodes_produced += t.ctr[0];
+        xwst.truncated_trees += t.ctr[1];
+        xwst.run_steps += c[xw::kRunSteps], xwst.skipped_entries += c[xw::kSkipped];
+        xwst.runs_queued += c[xw::kRunsQueued], xwst.items_queued += c[xw::kItemsQueued];
+        xwst.runs_self_copied += c[xw::kRunsSelf], xwst.runs_queue_full += c[xw::kRunsFull];
+        xwst.last_call_ms = ms_of_call();
+    }
+
     void count_via_finishes(const Tally &t, uint64_t *frontier, size_t n) {
         vst.list_finishes += t.ctr[3];
         vst.scan_finishes += t.ctr[4];
@@ -1113,6 +1237,10 @@ int ketogpu_subjects_new(const ketogpu_snapshot *sp, const ketogpu_subjects_opts
             h.list_cap = (uint32_t)std::min<long long>(std::max<long long>(atoll(e), 0), 1ll << 28);
         h.st.set_capacity = kSetCap;
         h.st.list_capacity = h.list_cap;
+        if (const char *e = getenv("KETOGPU_EXPAND_WIDE_QUEUE"))
+            h.xwq_cap = (uint64_t)std::min<long long>(std::max<long long>(atoll(e), 1), 1ll << 26);
+        h.xwst.queue_capacity = h.xwq_cap;
+        h.xwst.chunk = wide::kChunk;
     });
 }
 
@@ -1244,9 +1372,30 @@ int ketogpu_subjects_expand(ketogpu_subjects *h, const uint32_t *roots, const ui
         std::lock_guard<std::mutex> lk(h->mu);
         h->t0 = std::chrono::steady_clock::now();
         HIP_CHECK(hipSetDevice(h->device));
-        if (h->snapshot_ambiguous()) return h->expand_all_host(n, begin, count, status, needed);
+        if (h->snapshot_ambiguous()) return h->expand_all_host(h->xst, n, begin, count, status, needed);
         h->refresh(*h);
         h->run_expand(roots, rest_depth, n, out_nodes, out_children, capacity, begin, count, status, needed);
+    });
+}
+
+int ketogpu_subjects_expand_wide_stats_get(const ketogpu_subjects *h, ketogpu_expand_wide_stats *out) {
+    return list_stats_get(h, &ketogpu_subjects::xwst, out);
+}
+
+int ketogpu_subjects_expand_wide(ketogpu_subjects *h, const uint32_t *roots, const uint32_t *rest_depth, size_t n,
+                                 uint32_t *out_nodes, uint32_t *out_children, uint64_t capacity, uint64_t *begin,
+                                 uint64_t *count, uint32_t *status, uint64_t *needed) {
+    if (!h || !needed || (n && (!roots || !rest_depth || !begin || !count || !status)) ||
+        (capacity && (!out_nodes || !out_children)))
+        return einval("null argument");
+    if (n >= (1ull << 31)) return einval(h->what + ": more than 2^31 - 1 roots in one call");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->t0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipSetDevice(h->device));
+        if (h->snapshot_ambiguous()) return h->expand_all_host(h->xwst, n, begin, count, status, needed);
+        h->refresh(*h);
+        h->run_expand_wide(roots, rest_depth, n, out_nodes, out_children, capacity, begin, count, status, needed);
     });
 }
 

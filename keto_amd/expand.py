@@ -8,7 +8,8 @@ Engine is the host: ketogpu_expand, one tree per call with strings, and its twin
 ketogpu_snapshot_expand_ids, the same walk over a root that is a snapshot node, giving the
 tree as two preorder arrays (node ids and child counts).  DeviceEngine answers batches with
 ketogpu_subjects_expand, an ordered depth-first walk on the GPU that writes the same arrays
-(csrc/expand_tree.hpp).  Subjects that are no snapshot node (dynamic wildcard queries,
+(csrc/expand_tree.hpp), or with wide=True with ketogpu_subjects_expand_wide, the same walk with
+the copying of its leaf runs spread over the GPU (csrc/expand_wide.hpp).  Subjects that are no snapshot node (dynamic wildcard queries,
 unknown names) and requests the device hands back (status HOST: a query with an
 unknown-namespace row was met, or the snapshot has shared Subject.String() keys) go through
 Engine, so every answer, errors included, is Engine.BuildTree's.
@@ -145,10 +146,10 @@ class _IdTrees:
         from .lookup import resolve_subjects
         return resolve_subjects(self.snapshot, list(subjects))
 
-    def build_trees_json_batch(self, subjects, depths):
+    def build_trees_json_batch(self, subjects, depths, wide=False):
         """build_trees_batch as JSON strings ("null" for a nil tree; NotFound stays an object)"""
         return [t if isinstance(t, NotFound) else ("null" if t is None else t.MarshalJSON())
-                for t in self.build_trees_batch(subjects, depths)]
+                for t in self.build_trees_batch(subjects, depths, wide=wide)]
 
 
 class Engine(_IdTrees):
@@ -176,9 +177,10 @@ class Engine(_IdTrees):
         a, b = _take_ids(self.L, nodes, kids, n)
         return a, b, flags.value
 
-    def build_trees_batch(self, subjects, depths):
+    def build_trees_batch(self, subjects, depths, wide=False):
         """BuildTree per (subject, depth) -> a list of Tree | None | NotFound (returned, not
-        raised), through the host twin where the subject is a snapshot node"""
+        raised), through the host twin where the subject is a snapshot node.  `wide` is the
+        DeviceEngine's choice of call and means nothing here"""
         subjects = list(subjects)
         ids = self._resolve(subjects) if subjects else []
         res = []
@@ -299,33 +301,57 @@ class DeviceEngine(_IdTrees):
         L.check(self.L.ketogpu_subjects_expand_stats_get(self.subjects.h, C.byref(st)))
         return st.as_dict()
 
-    def expand_ids_raw(self, roots, depths, capacity=0):
-        """one ketogpu_subjects_expand call -> (nodes, num_children, begin, count, status,
-        needed): count[i] the exact size of tree i, begin[i] its offset in both arrays or
-        TRUNCATED / INVALID, status[i] EXPAND_OK / _NIL / _HOST; capacity 0 only counts.
-        depths: rest depths as the C call takes them (0 nil, EXPAND_DEPTH_ALL no limit)"""
+    def expand_wide_stats(self):
+        """ketogpu_expand_wide_stats of the handle ({} without one)"""
+        if self.subjects is None:
+            return {}
+        st = L.ExpandWideStats()
+        L.check(self.L.ketogpu_subjects_expand_wide_stats_get(self.subjects.h, C.byref(st)))
+        return st.as_dict()
+
+    def expand_ids_raw(self, roots, depths, capacity=0, wide=False, out=None):
+        """one ketogpu_subjects_expand call (wide: ketogpu_subjects_expand_wide) -> (nodes,
+        num_children, begin, count, status, needed): count[i] the exact size of tree i, begin[i]
+        its offset in both arrays or TRUNCATED / INVALID, status[i] EXPAND_OK / _NIL / _HOST;
+        capacity 0 only counts.  depths: rest depths as the C call takes them (0 nil,
+        EXPAND_DEPTH_ALL no limit).  out=(nodes, num_children): two C-contiguous uint32 arrays of
+        at least `capacity` words that the caller keeps; the call writes into them and returns
+        views of them instead of fresh arrays (ValueError for any other pair)"""
         roots = np.ascontiguousarray(roots, dtype=np.uint32)
         n = len(roots)
         depths = np.ascontiguousarray(np.broadcast_to(np.asarray(depths, dtype=np.uint32), (n,)))
         cap = int(capacity)
-        nodes = np.empty(max(cap, 1), dtype=np.uint32)
-        kids = np.empty(max(cap, 1), dtype=np.uint32)
+        if out is not None:
+            try:
+                nodes, kids = out
+            except (TypeError, ValueError):
+                raise ValueError("out: a pair (nodes, num_children) of uint32 arrays")
+            for a in (nodes, kids):
+                if not (isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.ndim == 1
+                        and a.flags.c_contiguous and a.flags.writeable and len(a) >= cap):
+                    raise ValueError("out: two writable C-contiguous uint32 arrays of at least `capacity` words")
+            if np.shares_memory(nodes, kids):
+                raise ValueError("out: the two arrays overlap")
+        else:
+            nodes = np.empty(max(cap, 1), dtype=np.uint32)
+            kids = np.empty(max(cap, 1), dtype=np.uint32)
         begin = np.zeros(max(n, 1), dtype=np.uint64)
         count = np.zeros(max(n, 1), dtype=np.uint64)
         status = np.full(max(n, 1), L.EXPAND_HOST, dtype=np.uint32)
         needed = C.c_uint64()
         if self.subjects is not None:
-            L.check(self.L.ketogpu_subjects_expand(
+            call = self.L.ketogpu_subjects_expand_wide if wide else self.L.ketogpu_subjects_expand
+            L.check(call(
                 self.subjects.h, roots.ctypes.data, depths.ctypes.data, n, nodes.ctypes.data if cap else None,
                 kids.ctypes.data if cap else None, cap, begin.ctypes.data, count.ctypes.data, status.ctypes.data,
                 C.byref(needed)))
         return nodes[:cap], kids[:cap], begin[:n], count[:n], status[:n], needed.value
 
-    def expand_ids(self, roots, depths):
+    def expand_ids(self, roots, depths, wide=False):
         """the trees of snapshot nodes: a count-only call, then a call with exactly the room
         -> (trees, status): trees[i] = (nodes, num_children) views, empty for NIL and HOST"""
-        *_, needed = self.expand_ids_raw(roots, depths, 0)
-        nodes, kids, begin, count, status, _ = self.expand_ids_raw(roots, depths, needed)
+        *_, needed = self.expand_ids_raw(roots, depths, 0, wide=wide)
+        nodes, kids, begin, count, status, _ = self.expand_ids_raw(roots, depths, needed, wide=wide)
         trees = []
         for b, c, st in zip(begin, count, status):
             if st != L.EXPAND_OK or not c:
@@ -336,7 +362,7 @@ class DeviceEngine(_IdTrees):
                 trees.append((nodes[int(b):int(b) + int(c)], kids[int(b):int(b) + int(c)]))
         return trees, status
 
-    def _batch(self, subjects, depths, make):
+    def _batch(self, subjects, depths, make, wide=False):
         subjects = list(subjects)
         depths = [depths] * len(subjects) if isinstance(depths, (int, np.integer)) else list(depths)
         ids = self._resolve(subjects) if subjects else np.zeros(0, np.uint32)
@@ -344,7 +370,8 @@ class DeviceEngine(_IdTrees):
         res = [None] * len(subjects)
         host = set(range(len(subjects))) - set(on_device)
         if on_device:
-            trees, status = self.expand_ids([ids[i] for i in on_device], [_depth32(depths[i]) for i in on_device])
+            trees, status = self.expand_ids([ids[i] for i in on_device], [_depth32(depths[i]) for i in on_device],
+                                            wide=wide)
             for i, (a, b), st in zip(on_device, trees, status):
                 if st == L.EXPAND_HOST:
                     host.add(i)
@@ -360,17 +387,19 @@ class DeviceEngine(_IdTrees):
                 res[i] = e
         return res
 
-    def build_trees_batch(self, subjects, depths):
+    def build_trees_batch(self, subjects, depths, wide=False):
         """BuildTree per (subject, depth) -> a list of Tree | None | NotFound (returned, not
-        raised): one device batch, and the host for what the device does not answer"""
-        return self._batch(subjects, depths, self.tree_from_ids)
+        raised): one device batch (wide: of the wide call), and the host for what the device
+        does not answer"""
+        return self._batch(subjects, depths, self.tree_from_ids, wide=wide)
 
-    def build_trees_json_batch(self, subjects, depths):
+    def build_trees_json_batch(self, subjects, depths, wide=False):
         """build_trees_batch as the library's JSON ("null" for a nil tree)"""
-        return ["null" if t is None else t for t in self._batch(subjects, depths, self.json_from_ids)]  # (NIL: None)
+        return ["null" if t is None else t
+                for t in self._batch(subjects, depths, self.json_from_ids, wide=wide)]  # (NIL: None)
 
-    def BuildTree(self, subject: Subject, rest_depth: int) -> Optional[Tree]:
-        t = self.build_trees_batch([subject], [rest_depth])[0]
+    def BuildTree(self, subject: Subject, rest_depth: int, wide=False) -> Optional[Tree]:
+        t = self.build_trees_batch([subject], [rest_depth], wide=wide)[0]
         if isinstance(t, NotFound):
             raise t
         return t

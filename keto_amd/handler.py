@@ -234,10 +234,15 @@ class Handler:
         per item, what GET /expand answers: the tree, null, or the error body (404 unknown
         namespace, 400 bad max-depth or subject).  max-depth is a JSON integer or a string as
         the query parameter takes it.  One batch of the expand engine serves the trees: on the
-        device where self.expand_batch is an expand.DeviceEngine, else the host's id walk."""
+        device where self.expand_batch is an expand.DeviceEngine, else the host's id walk.  The
+        form {"items": [...], "wide": true} asks the device engine for its chip-wide call."""
+        wide = False
         try:
             items = json.loads(body)
             if isinstance(items, dict):
+                wide = items.get("wide", False)
+                if not isinstance(wide, bool):
+                    raise BadRequest("expected a boolean for wide")
                 items = items["items"]
             if not isinstance(items, list):
                 raise BadRequest("expected a list of {subject, max-depth}")
@@ -270,7 +275,10 @@ class Handler:
                 continue
             subjects.append(subject), depths.append(max(-1, min(depth, 2**31 - 1))), where.append(i)
         engine = self.expand_batch if self.expand_batch is not None else self.expand
-        for i, t in zip(where, engine.build_trees_batch(subjects, depths)):
+        # (wide: the device engine's chip-wide call; the host engine takes and ignores it)
+        trees = engine.build_trees_batch(subjects, depths, wide=True) if wide else \
+            engine.build_trees_batch(subjects, depths)
+        for i, t in zip(where, trees):
             results[i] = self._error(404, str(t))[1] if isinstance(t, expand.NotFound) else (t.to_node() if t else None)
         return 200, results
 
