@@ -1416,7 +1416,10 @@ int ketogpu_subjects_page_via(ketogpu_subjects *h, const uint32_t *roots, const 
  * below its position, when the backlog's rows exceed a quarter of a full upload's bytes, when
  * the arena's tail is exhausted or its garbage passes max(num_edges / 4, 2^20) words (a
  * compaction), and on every version change under KETOGPU_LIST_REFRESH=full (env, read at
- * *_new).  KETOGPU_LIST_ARENA_SLACK (env, words) sets the arena's tail headroom.  The
+ * *_new).  KETOGPU_LIST_ARENA_SLACK (env, words) sets the arena's tail headroom, and
+ * KETOGPU_LIST_ARENA_GARBAGE (env, words, read at *_new) replaces the garbage bound
+ * max(num_edges / 4, 2^20); unset, the default holds.  fallbacks_trimmed is defensive: a
+ * registered reader is never trimmed past.  The
  * subjects handle's tier-2 bitmaps span num_nodes rounded up to a multiple of
  * KETOGPU_LIST_BOUND_STEP (env, default 32768), so that a new subject seldom moves the span:
  * when it does, tier 2's state is dropped and the next tier-2 call allocates it again.

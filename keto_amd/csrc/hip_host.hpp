@@ -183,6 +183,7 @@ struct ListHandle {
     ketogpu_list_refresh_stats rst{};
     bool refresh_full = false;    // KETOGPU_LIST_REFRESH=full: every version change uploads everything
     uint64_t slack_knob = ~0ull;  // KETOGPU_LIST_ARENA_SLACK: the arena's tail headroom in words (~0: the default)
+    uint64_t garbage_knob = ~0ull;  // KETOGPU_LIST_ARENA_GARBAGE: the garbage words a patch may leave (~0: the default)
     // A handle whose bound follows N (subjects) sizes tier 2's bitmaps for N rounded up to a
     // multiple of this (KETOGPU_LIST_BOUND_STEP; at most 1024 more zero words per bitmap), so that
     // a write that adds a subject seldom moves the bound: dropping tier 2's state costs the next
@@ -330,7 +331,9 @@ struct ListHandle {
             sg[0] = at, sg[1] = words, sg[2] = len, sg[3] = (arena ? kSegRowBounds : kSegRow) << 32 | v;
             words += len;
         }
-        if (arena && garbage > std::max<uint64_t>(s.stats.num_edges / 4, 1ull << 20)) {
+        const uint64_t garbage_max =
+            garbage_knob != ~0ull ? garbage_knob : std::max<uint64_t>(s.stats.num_edges / 4, 1ull << 20);
+        if (arena && garbage > garbage_max) {
             rst.compactions++;
             return false;
         }
@@ -800,6 +803,7 @@ int list_new(const ketogpu_snapshot *sp, const Opts *opts, H **out, const char *
         if (const char *e = getenv(slots_knob)) h->slot_cap = (uint32_t)std::max(atoi(e), 0);
         if (const char *e = getenv("KETOGPU_LIST_REFRESH")) h->refresh_full = std::string(e) == "full";
         if (const char *e = getenv("KETOGPU_LIST_ARENA_SLACK")) h->slack_knob = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KETOGPU_LIST_ARENA_GARBAGE")) h->garbage_knob = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KETOGPU_LIST_BOUND_STEP"))
             h->bound_step = (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(strtoull(e, nullptr, 10), 1), 1u << 24);
         init(*h);

@@ -227,6 +227,8 @@ struct IdExpander {
 
     void run(uint32_t root, uint32_t depth) {
         if (!depth) return;
+        // a writable snapshot's placeholder stands for no subject: the nil tree, as the device answers
+        if (root == s.Df || root == s.Dbi || root == s.Dbo) return;
         if (s.node_kind[root] != KETOGPU_SUBJECT_SET) return emit(root, 0);
         struct Frame {
             uint32_t v, depth;  // depth: the children's rest depth, >= 1

@@ -248,14 +248,20 @@ def structure(side_name):
     return snap, Twin(side, snap), Truth(side, snap), side.structure(snap)
 
 
+def writable_chain_rows():
+    """two chains, u0 <- a0 <- a1 <- spare and u1 <- b0 <- b1 <- b2"""
+    s, ss = LC.sid, LC.sset
+    return [s("a0", "member", "u0"), ss("a1", "member", "a0", "member"), ss("spare", "member", "a1", "member"),
+            s("b0", "member", "u1"), ss("b1", "member", "b0", "member"), ss("b2", "member", "b1", "member")]
+
+
 def writable_chains(side):
     """a writable snapshot with two chains, u0 <- a0 <- a1 <- spare and u1 <- b0 <- b1 <- b2, and
     a write that hangs the second under the first (b0 now holds a1#member): a start's deepest
     member moves from 3 to 5 hops -> (snapshot, start, rows to write).  A writable snapshot pads
     its rows with placeholder nodes, which are interior ids but no members."""
-    s, ss = LC.sid, LC.sset
-    rows = [s("a0", "member", "u0"), ss("a1", "member", "a0", "member"), ss("spare", "member", "a1", "member"),
-            s("b0", "member", "u1"), ss("b1", "member", "b0", "member"), ss("b2", "member", "b1", "member")]
+    ss = LC.sset
+    rows = writable_chain_rows()
     snap = Snapshot.from_rows(LC.NS1, rows, writable=True)
     x = side.node(snap, "u0") if side is LookupSide else side.set_node(snap, "b2")
     return snap, x, [ss("b0", "member", "a1", "member")]
