@@ -447,6 +447,17 @@ int ketogpu_engine_piped_full_requests(ketogpu_engine *e, uint64_t *out);
 /* diagnostics: plan label's first-stage launches on this engine so far in which a wave ran two
  * units of 16 requests (KETOGPU_LABEL_PAIR) */
 int ketogpu_engine_label_pair_launches(ketogpu_engine *e, uint64_t *out);
+/* diagnostics: queued first-stage launches on this engine so far that read the S head first
+ * and the P head only where S leaves the answer open (KETOGPU_LABEL_SFIRST: 1, the default,
+ * at 32/32 heads; 2 every queued launch but one — at 8/64 heads with two units per wave the
+ * flagged kernel would pass 64 VGPRs and lose a wave per SIMD against its unflagged twin, so
+ * it is launched as it was; the flag needs the tail phase, KETOGPU_LABEL_TAIL) */
+int ketogpu_engine_label_sfirst_launches(ketogpu_engine *e, uint64_t *out);
+/* diagnostics: the requests whose P head those launches did not read, summed over the
+ * engine's launches so far.  Counted only on an engine created with
+ * KETOGPU_LABEL_SFIRST_COUNT=1 (else 0: lean launches carry no counter).  Waits for the
+ * engine's queued calls. */
+int ketogpu_engine_label_one_head_requests(ketogpu_engine *e, uint64_t *out);
 void ketogpu_queries_free(ketogpu_queries *q);
 
 /* statistics of the last run on this engine (for the roofline report) */

@@ -480,6 +480,8 @@ SIGNATURES = {
     "ketogpu_engine_wait": (C.c_int, [vp]),
     "ketogpu_engine_piped_full_requests": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "ketogpu_engine_label_pair_launches": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_engine_label_sfirst_launches": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "ketogpu_engine_label_one_head_requests": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "ketogpu_probe_random_lines": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "ketogpu_probe_random_lines_streams": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
                                                      C.POINTER(C.c_double)]),

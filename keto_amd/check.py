@@ -173,6 +173,20 @@ class Engine:
         L.check(self.L.ketogpu_engine_label_pair_launches(self.h, C.byref(n)))
         return n.value
 
+    def label_sfirst_launches(self):
+        """queued first-stage launches so far that read S first and P only where S leaves the
+        answer open (KETOGPU_LABEL_SFIRST)"""
+        n = C.c_uint64()
+        L.check(self.L.ketogpu_engine_label_sfirst_launches(self.h, C.byref(n)))
+        return n.value
+
+    def label_one_head_requests(self):
+        """the requests whose P head those launches skipped (counted with
+        KETOGPU_LABEL_SFIRST_COUNT=1 only, else 0); waits for the queued calls"""
+        n = C.c_uint64()
+        L.check(self.L.ketogpu_engine_label_one_head_requests(self.h, C.byref(n)))
+        return n.value
+
     def set_events(self, every_kernel):
         """host-to-host batches: a timing event between the call's kernels (main_ms = the
         first stage's own time) or only around the call (default)"""

@@ -2713,11 +2713,101 @@ __device__ __forceinline__ void label_heads(const LabelGraph &L, uint32_t r, uin
     }
 }
 
-template <int HS, int HP, bool TAIL>
+// S's inline landmarks: its inline entries below Ni (the raw entries follow them), counted
+// in the registers (pads are 0xFFFFFFFF) and summed over the request's four lanes by DPP
+template <int HS>
+__device__ __forceinline__ uint32_t label_s_landmarks(const LabelGraph &L, const uint32_t (&sw)[HS / 4]) {
+    constexpr int SW = HS / 4;
+    // this lane's words of the S head that are entries (the header is words 0-3 of the head:
+    // the first lane's, or with 2 words per lane the first two lanes')
+    const bool s_body = (threadIdx.x & 3) * SW >= kHeadFixed;
+    uint32_t es = 0;
+#pragma unroll
+    for (int k = 0; k < SW; k++) es += (k >= (int)kHeadFixed || s_body) && sw[k] < L.ni;
+    es += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)es, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
+    es += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)es, 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
+    return es;
+}
+// the one-edge test: a non-interior root among S's inline raw entries, each lane against
+// its own words (a landmark is below Ni and a pad no node id: neither equals such a root)
+template <int HS>
+__device__ __forceinline__ bool label_s_edge(const LabelGraph &L, uint32_t r, const uint32_t (&sw)[HS / 4]) {
+    constexpr int SW = HS / 4;
+    const bool s_body = (threadIdx.x & 3) * SW >= kHeadFixed;
+    bool head = false, body = false;
+#pragma unroll
+    for (int k = 0; k < SW; k++) (k < (int)kHeadFixed ? head : body) |= sw[k] == r;
+    return r >= L.ni && (body | (head & s_body));
+}
+
+// SFIRST (queued lean calls only, label_carry_kernel with TAIL; KETOGPU_LABEL_SFIRST): the S
+// head is read first, and P(r) only where S(t) leaves the answer open.  Two classes are
+// decided by S alone, whatever P(r) holds:
+//   one-edge hit   r is among S(t)'s inline raw entries (a direct grant): label_settle's
+//                  one-edge test hits, and a hit neither reads P's list nor lists a record;
+//   settled false  S's mask is zero (no mask hit), S has no inline landmark (es == 0: step 1
+//                  walks nothing, the tail phase wants es > 0, and lm_done holds for any P)
+//                  and the one-edge test is settled by S (raw_done, which P is no part of).
+// Such a request settles exactly as if P(r) were an empty list with a zero mask: its P
+// registers get that image (count, overflow start and mask zero, pads for entries) instead of
+// a read.  That P's count is never seen is sound because queued calls run only on engines
+// where label_rest_free holds: no head is marked kNoLabel there, so `labelled` is `valid`
+// whatever P(r) says (were the pads left in the header, np would read as kNoLabel and the
+// request be listed for the second stage).  The launch path asserts the queued path.
+// This is one more dependent read per wave, for one line less per request of the class.
+//
+// the S step: this lane's words of S(t), pads where the request reads none
+template <int HS>
+__device__ __forceinline__ void label_head_s(const LabelGraph &L, uint32_t r, uint32_t t, uint32_t (&sw)[HS / 4]) {
+    const bool valid = r != KETOGPU_NODE_NONE && t != KETOGPU_NODE_NONE && r < kDynBase;
+#pragma unroll
+    for (int k = 0; k < HS / 4; k++) sw[k] = 0xFFFFFFFFu;
+    if (valid) label_head_load<HS / 4>(L.S + (uint64_t)t * HS, threadIdx.x & 3, sw);
+}
+// S alone decides the request (its four lanes agree); es, edge: label_s_landmarks, label_s_edge
+template <int HS>
+__device__ __forceinline__ bool label_s_decides(const LabelGraph &L, uint32_t r, uint32_t t,
+                                                const uint32_t (&sw)[HS / 4], uint32_t es, bool edge) {
+    constexpr int SW = HS / 4;
+    constexpr uint32_t CS = HS - kHeadFixed;
+    const bool valid = r != KETOGPU_NODE_NONE && t != KETOGPU_NODE_NONE && r < kDynBase;
+    int any = edge;  // on any of the four lanes
+    any |= __builtin_amdgcn_update_dpp(0, any, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
+    any |= __builtin_amdgcn_update_dpp(0, any, 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
+    const uint32_t ns = label_word<SW, 0>(sw), sm = label_word<SW, 2>(sw) | label_word<SW, 3>(sw);
+    // S's last inline entry: the last word of the fourth lane
+    const uint32_t s_end = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sw[SW - 1], 0xFF, 0xf, 0xf, false);
+    const bool raw_done = r < L.ni || ns <= CS || r <= s_end;
+    return valid && (any != 0 || (sm == 0 && es == 0 && raw_done));
+}
+// the P step: this lane's words of P(r); pads where the request reads none, an empty list's
+// head where S decided (`decided`)
+template <int HP>
+__device__ __forceinline__ void label_head_p(const LabelGraph &L, uint32_t r, uint32_t t, bool decided,
+                                             uint32_t (&pw)[HP / 4]) {
+    constexpr int PW = HP / 4;
+    const uint32_t sub = threadIdx.x & 3;
+    const bool valid = r != KETOGPU_NODE_NONE && t != KETOGPU_NODE_NONE && r < kDynBase;
+#pragma unroll
+    for (int k = 0; k < PW; k++) pw[k] = decided && sub * PW + k < kHeadFixed ? 0u : 0xFFFFFFFFu;
+    if (valid && !decided) label_head_load<PW>(L.P + (uint64_t)r * HP, sub, pw);
+}
+// the requests of this unit whose P read was skipped, counted where a counter is given
+// (wave-uniform; KETOGPU_LABEL_SFIRST_COUNT): one atomic per unit that has one
+__device__ __forceinline__ void label_count_decided(unsigned long long *one_head, bool decided) {
+    if (!one_head) return;
+    const uint64_t b = __ballot(decided && (threadIdx.x & 3) == 0);
+    if (b && (threadIdx.x & 63) == 0) atomicAdd(one_head, (unsigned long long)__popcll(b));
+}
+
+// SFIRST: S's inline landmark count and this lane's one-edge result come from the caller
+// (es_s, edge_s: label_s_landmarks and label_s_edge, worked out once before the P read)
+template <int HS, int HP, bool TAIL, bool SFIRST = false>
 __device__ __forceinline__ void label_settle(LabelShared<HS, HP> &sh, const LabelGraph &L, const uint32_t r,
                                              const uint32_t t, const uint32_t (&sw)[HS / 4],
                                              const uint32_t (&pw)[HP / 4], uint64_t *allowed, const uint64_t unit,
-                                             const LabelRest &R, const LabelRest &F, unsigned long long *stats) {
+                                             const LabelRest &R, const LabelRest &F, unsigned long long *stats,
+                                             const uint32_t es_s = 0, const bool edge_s = false) {
     static_assert((HS == 8 || HS == 16 || HS == 32 || HS == 64) && (HP == 8 || HP == 16 || HP == 32 || HP == 64),
                   "heads of 8, 16, 32 or 64 words");
     constexpr int SW = HS / 4, PW = HP / 4;                                   // head words per lane
@@ -2748,15 +2838,21 @@ __device__ __forceinline__ void label_settle(LabelShared<HS, HP> &sh, const Labe
     // S's inline landmarks: its inline entries below Ni (the raw entries follow them), counted
     // in the registers (pads are 0xFFFFFFFF) and summed over the request's four lanes by DPP
     uint32_t es = 0;
+    if constexpr (SFIRST) {
+        es = es_s;
+    } else {
 #pragma unroll
-    for (int k = 0; k < SW; k++) es += (k >= (int)kHeadFixed || s_body) && sw[k] < L.ni;
-    es += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)es, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
-    es += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)es, 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
+        for (int k = 0; k < SW; k++) es += (k >= (int)kHeadFixed || s_body) && sw[k] < L.ni;
+        es += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)es, 0xB1, 0xf, 0xf, false);  // quad_perm [1,0,3,2]
+        es += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)es, 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
+    }
     if (!labelled) es = 0;
     const uint32_t ep = min(np, CP);
     // the one-edge test: a non-interior root among S's inline raw entries, each lane against
     // its own words (a landmark is below Ni and a pad no node id: neither equals such a root)
-    {
+    if constexpr (SFIRST) {
+        hit |= labelled && edge_s;
+    } else {
         bool head = false, body = false;
 #pragma unroll
         for (int k = 0; k < SW; k++) (k < (int)kHeadFixed ? head : body) |= sw[k] == r;
@@ -2889,15 +2985,26 @@ __device__ __forceinline__ void label_settle(LabelShared<HS, HP> &sh, const Labe
 }
 
 // one unit; r_lane, t_lane: request j's ids on lane j < 16
-template <int HS, int HP, bool TAIL = false>
+template <int HS, int HP, bool TAIL = false, bool SFIRST = false>
 __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelGraph &L, uint32_t r_lane,
                                            uint32_t t_lane, uint64_t *allowed, const uint64_t unit,
-                                           const LabelRest &R, const LabelRest &F, unsigned long long *stats) {
+                                           const LabelRest &R, const LabelRest &F, unsigned long long *stats,
+                                           unsigned long long *one_head = nullptr) {
     const uint32_t q = (threadIdx.x & 63) >> 2;
     const uint32_t r = (uint32_t)__shfl((int)r_lane, (int)q, 64), t = (uint32_t)__shfl((int)t_lane, (int)q, 64);
     uint32_t sw[HS / 4], pw[HP / 4];
-    label_heads<HS, HP>(L, r, t, sw, pw);
-    label_settle<HS, HP, TAIL>(sh, L, r, t, sw, pw, allowed, unit, R, F, stats);
+    if constexpr (SFIRST) {  // S, then P where S leaves the request open
+        label_head_s<HS>(L, r, t, sw);
+        const uint32_t es = label_s_landmarks<HS>(L, sw);
+        const bool edge = label_s_edge<HS>(L, r, sw);
+        const bool decided = label_s_decides<HS>(L, r, t, sw, es, edge);
+        label_head_p<HP>(L, r, t, decided, pw);
+        label_count_decided(one_head, decided);
+        label_settle<HS, HP, TAIL, true>(sh, L, r, t, sw, pw, allowed, unit, R, F, stats, es, edge);
+    } else {
+        label_heads<HS, HP>(L, r, t, sw, pw);
+        label_settle<HS, HP, TAIL>(sh, L, r, t, sw, pw, allowed, unit, R, F, stats);
+    }
 }
 
 // Two consecutive units (`unit` even, and unit + 1 where `two`) by one wave
@@ -2912,12 +3019,14 @@ __device__ __forceinline__ void label_unit(LabelShared<HS, HP> &sh, const LabelG
 // and statistics are per unit), both in the one image — the second unit's heads wait in
 // registers — so a CU holds as many waves as with a unit per wave (two images would halve
 // them at 32-word heads: LDS).  Without `two` (the last unit has no partner) the second unit
-// is neither read nor written.
-template <int HS, int HP, bool TAIL>
+// is neither read nor written.  SFIRST: both units' S reads are issued together, then both
+// units' P reads for the requests S leaves open.
+template <int HS, int HP, bool TAIL, bool SFIRST = false>
 __device__ __forceinline__ void label_pair(LabelShared<HS, HP> &sh, const LabelGraph &L, const uint32_t *roots,
                                            const uint32_t *targets, uint64_t n, uint64_t *allowed,
                                            const uint64_t unit, const bool two, const LabelRest &R,
-                                           const LabelRest &F, unsigned long long *stats) {
+                                           const LabelRest &F, unsigned long long *stats,
+                                           unsigned long long *one_head = nullptr) {
     const uint32_t lane = threadIdx.x & 63, q = lane >> 2;
     const uint64_t c = unit * 16 + (lane & 31);
     uint32_t v = KETOGPU_NODE_NONE;
@@ -2929,12 +3038,30 @@ __device__ __forceinline__ void label_pair(LabelShared<HS, HP> &sh, const LabelG
         t1 = (uint32_t)__shfl((int)v, (int)(48 + q), 64);
     }
     uint32_t sw0[HS / 4], pw0[HP / 4], sw1[HS / 4], pw1[HP / 4];
-    label_heads<HS, HP>(L, r0, t0, sw0, pw0);
-    label_heads<HS, HP>(L, r1, t1, sw1, pw1);
-    label_settle<HS, HP, TAIL>(sh, L, r0, t0, sw0, pw0, allowed, unit, R, F, stats);
-    if (two) {
-        wave_sync();  // (the first unit's reads of the image are behind)
-        label_settle<HS, HP, TAIL>(sh, L, r1, t1, sw1, pw1, allowed, unit + 1, R, F, stats);
+    if constexpr (SFIRST) {
+        label_head_s<HS>(L, r0, t0, sw0);
+        label_head_s<HS>(L, r1, t1, sw1);
+        const uint32_t es0 = label_s_landmarks<HS>(L, sw0), es1 = label_s_landmarks<HS>(L, sw1);
+        const bool edge0 = label_s_edge<HS>(L, r0, sw0), edge1 = label_s_edge<HS>(L, r1, sw1);
+        const bool dec0 = label_s_decides<HS>(L, r0, t0, sw0, es0, edge0);
+        const bool dec1 = label_s_decides<HS>(L, r1, t1, sw1, es1, edge1);
+        label_head_p<HP>(L, r0, t0, dec0, pw0);
+        label_head_p<HP>(L, r1, t1, dec1, pw1);
+        label_count_decided(one_head, dec0);
+        label_count_decided(one_head, dec1);
+        label_settle<HS, HP, TAIL, true>(sh, L, r0, t0, sw0, pw0, allowed, unit, R, F, stats, es0, edge0);
+        if (two) {
+            wave_sync();  // (the first unit's reads of the image are behind)
+            label_settle<HS, HP, TAIL, true>(sh, L, r1, t1, sw1, pw1, allowed, unit + 1, R, F, stats, es1, edge1);
+        }
+    } else {
+        label_heads<HS, HP>(L, r0, t0, sw0, pw0);
+        label_heads<HS, HP>(L, r1, t1, sw1, pw1);
+        label_settle<HS, HP, TAIL>(sh, L, r0, t0, sw0, pw0, allowed, unit, R, F, stats);
+        if (two) {
+            wave_sync();  // (the first unit's reads of the image are behind)
+            label_settle<HS, HP, TAIL>(sh, L, r1, t1, sw1, pw1, allowed, unit + 1, R, F, stats);
+        }
     }
 }
 
@@ -3209,10 +3336,15 @@ __global__ __launch_bounds__(64) void label_full_kernel(LabelGraph L, uint64_t *
 // role finds about a sixth of the records (config #2).
 // PAIR: workgroup D + b is units 2 b and 2 b + 1 (label_pair), so the grid is
 // D + ceil(units / 2).
-template <int HS, int HP, bool TAIL, bool PAIR = false>
+// SFIRST (with TAIL only): the first stage reads S first and P only where S leaves the
+// request open (label_head_s); one_head, where given, counts the requests whose P read was
+// skipped.
+template <int HS, int HP, bool TAIL, bool PAIR = false, bool SFIRST = false>
 __global__ __launch_bounds__(64) void label_carry_kernel(LabelGraph L, const uint32_t *roots, const uint32_t *targets,
                                                          uint64_t n, uint64_t *allowed, LabelRest R, LabelRest F,
-                                                         LabelRest Fd, uint64_t *allowed_d, uint32_t D) {
+                                                         LabelRest Fd, uint64_t *allowed_d, uint32_t D,
+                                                         unsigned long long *one_head) {
+    static_assert(TAIL || !SFIRST, "S first is built with the tail phase only");
     __shared__ LabelShared<HS, HP> sh;
     static_assert(sizeof(LabelShared<HS, HP>) == 64 * (HS + HP + 8), "the dense role's stage");
     if (blockIdx.x < D) {  // (a whole workgroup: one wave)
@@ -3229,13 +3361,13 @@ __global__ __launch_bounds__(64) void label_carry_kernel(LabelGraph L, const uin
     if constexpr (PAIR) {
         unit = 2 * (uint64_t)(blockIdx.x - D);
         const bool two = unit + 1 < units;
-        label_pair<HS, HP, TAIL>(sh, L, roots, targets, n, allowed, unit, two, R, F, nullptr);
+        label_pair<HS, HP, TAIL, SFIRST>(sh, L, roots, targets, n, allowed, unit, two, R, F, nullptr, one_head);
         unit += two;
     } else {
         unit = blockIdx.x - D;
         uint32_t r, t;
         bidi_load_rt<16>(unit, units, roots, targets, n, r, t);
-        label_unit<HS, HP, TAIL>(sh, L, r, t, allowed, unit, R, F, nullptr);
+        label_unit<HS, HP, TAIL, SFIRST>(sh, L, r, t, allowed, unit, R, F, nullptr, one_head);
     }
     // the last result word's 16-bit parts past the last unit (no unit writes them)
     if (unit + 1 == units && threadIdx.x == 0)
@@ -4967,6 +5099,35 @@ struct ketogpu_engine {
     bool pair_carry() const { return label_pair_mode >= 2 || (label_pair_mode == 1 && label_hs == 32 && label_hp == 32); }
     bool pair_sync() const { return label_pair_mode >= 2; }
     uint64_t pair_launches = 0;  // launches with two units per wave (ketogpu_engine_label_pair_launches)
+    // KETOGPU_LABEL_SFIRST: a queued call's first stage reads the S head first and the P head
+    // only where S leaves the answer open (label_head_s; built with the tail phase only, so
+    // KETOGPU_LABEL_TAIL=0 launches without it).  1: in the launches where that was measured
+    // to gain (sfirst_measured); 2: every queued launch at every head pair but the one that
+    // sfirst_fits leaves out (measurements and tests); 0: none.  Default 1.
+    int label_sfirst_mode = [] {
+        const char *e = getenv("KETOGPU_LABEL_SFIRST");
+        return e ? atoi(e) : 1;
+    }();
+    // the head pairs at which S first beat the kernel as it was beyond the spread: 32/32
+    // (config #2: every run above the parent's best, profiles/r11/ab_sfirst; the social
+    // shape +17%).  64/64 loses 4-6% (folders, profiles/r11/shapes.jsonl); the other head
+    // pairs are not measured yet
+    bool sfirst_measured() const { return label_hs == 32 && label_hp == 32; }
+    // the one instantiation that the flag takes past 64 VGPRs, and so from 8 to 7 waves per
+    // SIMD, is never launched with it: 8/64 heads paired (65 against 64, profiles/r11/static.txt;
+    // every other head pair keeps its unflagged twin's occupancy, paired and unpaired)
+    bool sfirst_fits() const { return !(pair_carry() && label_hs == 8 && label_hp == 64); }
+    bool sfirst_carry() const {
+        return label_tail && sfirst_fits() && (label_sfirst_mode >= 2 || (label_sfirst_mode == 1 && sfirst_measured()));
+    }
+    uint64_t sfirst_launches = 0;  // launches that read S first (ketogpu_engine_label_sfirst_launches)
+    // KETOGPU_LABEL_SFIRST_COUNT=1: those launches count the requests whose P read they skip
+    // (ketogpu_engine_label_one_head_requests); lean timed runs pass the kernel no counter
+    bool sfirst_count = [] {
+        const char *e = getenv("KETOGPU_LABEL_SFIRST_COUNT");
+        return e && atoi(e) != 0;
+    }();
+    unsigned long long *d_one_head = nullptr;
     // the requests the most recent flushed pass of a queued call found listed: queued calls
     // list fewer than synchronized ones (the tail phase), so their passes are sized by their
     // own count.  label_full_kernel writes its list's total into the host-mapped mirror; it
@@ -5877,6 +6038,11 @@ struct ketogpu_engine {
         HIP_CHECK(hipHostGetDevicePointer((void **)&d_hctr, h_ctr, 0));
         d_bad = dalloc<unsigned long long>(1);
         owned.push_back(d_bad);
+        if (sfirst_count) {
+            d_one_head = dalloc<unsigned long long>(1);
+            owned.push_back(d_one_head);
+            HIP_CHECK(hipMemsetAsync(d_one_head, 0, sizeof(unsigned long long), stream));  // (synchronized below)
+        }
         HIP_CHECK(hipStreamSynchronize(stream));
         build_hubs(s);
     }
@@ -6633,20 +6799,29 @@ struct ketogpu_engine {
                     PendingDense p = pend[cur_pipe];
                     pend[cur_pipe] = PendingDense{};
                     const unsigned D = p.on ? piped_grid() : 0u;
+                    // S first leaves P's count unseen: sound only where no head is kNoLabel,
+                    // which is what makes a call a queued one (label_rest_free)
+                    const bool sfirst = sfirst_carry();
+                    if (sfirst && !(pipelined_req && label_rest_free(q)))
+                        throw Error(KETOGPU_EDEVICE, "internal: an S-first launch outside the queued path");
                     label_dispatch([&](auto hs, auto hp) {
-                        auto go = [&](auto tail, auto pair) {
+                        auto go = [&](auto tail, auto pair, auto sf) {
                             const unsigned first = (unsigned)(decltype(pair)::value ? (bunits + 1) / 2 : bunits);
-                            KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value,
-                                                        decltype(tail)::value, decltype(pair)::value>),
+                            KLAUNCH((label_carry_kernel<decltype(hs)::value, decltype(hp)::value, decltype(tail)::value,
+                                                        decltype(pair)::value, decltype(sf)::value>),
                                     dim3(D + first), dim3(64), lds_pad, stream, lgraph, q.roots, q.targets, q.n,
-                                    q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D);
+                                    q.allowed, label_rest(q.n), label_full(q.n), p.F, p.allowed, D,
+                                    decltype(sf)::value ? d_one_head : nullptr);
                         };
-                        if (label_tail && pair_carry()) go(std::true_type{}, std::true_type{});
-                        else if (label_tail) go(std::true_type{}, std::false_type{});
-                        else if (pair_carry()) go(std::false_type{}, std::true_type{});
-                        else go(std::false_type{}, std::false_type{});
+                        if (sfirst && pair_carry()) go(std::true_type{}, std::true_type{}, std::true_type{});
+                        else if (sfirst) go(std::true_type{}, std::false_type{}, std::true_type{});
+                        else if (label_tail && pair_carry()) go(std::true_type{}, std::true_type{}, std::false_type{});
+                        else if (label_tail) go(std::true_type{}, std::false_type{}, std::false_type{});
+                        else if (pair_carry()) go(std::false_type{}, std::true_type{}, std::false_type{});
+                        else go(std::false_type{}, std::false_type{}, std::false_type{});
                     });
                     pair_launches += pair_carry();
+                    sfirst_launches += sfirst;
                     if (p.q) p.q->pass = 2;
                 } else if (!src) {
                     launch_bidi(bidi_cfg, (unsigned)bunits, lds_pad, q, nullptr, nullptr, list[0], &spill_count[0],
@@ -7571,6 +7746,29 @@ int ketogpu_engine_label_pair_launches(ketogpu_engine *e, uint64_t *out) {
     if (!e || !out) throw Error(KETOGPU_EINVAL, "null argument");
     std::lock_guard<std::mutex> lk(e->mu);
     *out = e->pair_launches;
+    API_END
+}
+
+int ketogpu_engine_label_sfirst_launches(ketogpu_engine *e, uint64_t *out) {
+    API_BEGIN
+    if (!e || !out) throw Error(KETOGPU_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    *out = e->sfirst_launches;
+    API_END
+}
+
+int ketogpu_engine_label_one_head_requests(ketogpu_engine *e, uint64_t *out) {
+    API_BEGIN
+    if (!e || !out) throw Error(KETOGPU_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(e->mu);
+    unsigned long long v = 0;
+    if (e->d_one_head) {  // (waits for the queued calls: the counter is complete)
+        HIP_CHECK(hipSetDevice(e->device));
+        e->drain_pipe();
+        HIP_CHECK(hipStreamSynchronize(e->stream));
+        HIP_CHECK(hipMemcpy(&v, e->d_one_head, sizeof v, hipMemcpyDeviceToHost));
+    }
+    *out = v;
     API_END
 }
 
